@@ -10,9 +10,13 @@ synthetic 8K (7680x4320, 4:2:0, 10-bit) random-access frame = 2040 CTUs of 128x1
     -> boundary strengths from the side tables -> deblock (vertical, horizontal; luma + chroma) -> SAO
     -> ALF (luma classify + filter, chroma, cross-component); the loop filters through their table-driven stage drivers
 
-Timing: W warm-up steps; an untimed pass of K steps with HIP events around every stage (the ``stages`` breakdown and which
-stage dominates); then the timed region: exactly K steps between barrier + synchronize, HIP events around the dominant
-stage only (``roofline``).  ``--graph`` replays the step as one captured hipGraph in the timed region instead.
+Timing: W warm-up steps, then the timed region: exactly K steps between barrier + synchronize (``ms_per_step``).  A plain run
+does only that and prints the headline line.  ``--full`` adds the secondary figures: before the timed region an untimed pass of
+K steps with HIP events around every stage (the ``stages`` breakdown and which stage dominates), HIP events around the dominant
+stage inside the timed region (``roofline``), then the independent-frames and upload legs, the device copy rate, the oracle
+check (``verified``) and the CPU baseline.  ``--graph`` replays the step as one captured hipGraph in the timed region instead.
+
+``--dump-outputs DIR`` writes what the timed region decoded in its last step, as DIR/<name>.npy (see dump_outputs).
 
 Frames are independent, so ranks share nothing: weak scaling, no data-path collective and no RCCL (torch.distributed over gloo
 carries one barrier and the max-over-ranks of the elapsed time).  ``python bench.py --gpus N`` on its own starts the N ranks
@@ -836,13 +840,16 @@ def build_chain(lib, torch, fr):
     lfj["max_x"], lfj["max_y"], lfj["qp"], lfj["dequant"], lfj["dep_quant"] = win_w[lfi] - 1, win_h[lfi] - 1, itj["dq_qp"][lfi], 1, rng_t.integers(0, 2, size=len(lfi))
     lfj["bit_depth"], lfj["range"], lfj["log2_matrix_size"], lfj["dc"] = bd, 15, 1, -1
     lfj["pred_mode_intra"], lfj["lfnst_idx"] = rng_t.integers(-14, 81, size=len(lfi)), itj["lfnst_idx"][lfi]
-    # zero the levels outside the windows (one pass over the pristine copy, host-built imask)
-    imask = np.zeros(max(1, work.resid_len), np.int32)
-    for k in range(n_tb):
-        w_, o_ = int(tw[k]), int(itb[k, 5])
-        m2 = imask[o_:o_ + int(tw[k] * th[k])].reshape(int(th[k]), w_)
-        m2[:int(win_h[k]), :int(win_w[k])] = 1
-    levels0 *= torch.from_numpy(imask).cuda()
+    # zero the levels outside the windows (one pass over the pristine copy, host-built imask; like `work` and the draws of rng_t it is
+    # the same for every frame object of a run, so it is built once)
+    if ("imask",) + wkey not in _GENERATED:
+        imask = np.zeros(max(1, work.resid_len), np.int32)
+        for k in range(n_tb):
+            w_, o_ = int(tw[k]), int(itb[k, 5])
+            m2 = imask[o_:o_ + int(tw[k] * th[k])].reshape(int(th[k]), w_)
+            m2[:int(win_h[k]), :int(win_w[k])] = 1
+        _GENERATED[("imask",) + wkey] = imask
+    levels0 *= torch.from_numpy(_GENERATED[("imask",) + wkey]).cuda()
     area_class = np.select([tlw + tlh <= 4, tlw + tlh <= 6, tlw + tlh <= 8, tlw + tlh <= 10], [4, 6, 8, 10], 12)
     tb_order = np.argsort(area_class, kind="stable")
     itj_sorted = itj[tb_order]
@@ -930,28 +937,32 @@ def build_chain(lib, torch, fr):
             env.stats["recon_intra_ctus"] = int(len(work.order))
             return len(work.order), bad
 
-        intra_samples = int(sum(int(c[3]) * int(c[4]) for c in work.cmds[work.cmds["kind"] == abi.RECON_MARK] if c[11] == 0)) * 3 // 2
-        # what bounds this stage is not bandwidth but the longest chain of dependent CTUs (left, upper-left, upper, upper-right
-        # neighbours that have commands), each walked by one wave per channel type: its length in CTUs and in commands
-        ncx_ = fr.ncx if hasattr(fr, "ncx") else (fr.width + CTB - 1) // CTB
-        ncmd = work.ctus["n_cmd"].astype(np.int64)
-        depth_c, depth_k = np.zeros(len(ncmd), np.int64), np.zeros(len(ncmd), np.int64)
-        cflags = work.ctus["flags"].astype(np.int64)
-        for rs in work.order:
-            rs = int(rs)
-            rx_, best_c, best_k = rs % ncx_, 0, 0
-            if cflags[rs] & abi.RECON_CTU_LIGHT:      # waits for the luma of the flagged neighbours only
-                deps_ = ((rs - 1) if (rx_ and cflags[rs] & abi.RECON_CTU_LUMA_LEFT) else -1, (rs - ncx_) if cflags[rs] & abi.RECON_CTU_LUMA_UP else -1)
-            else:
-                deps_ = ((rs - 1) if rx_ else -1, (rs - ncx_ - 1) if rx_ else -1, rs - ncx_, (rs - ncx_ + 1) if rx_ + 1 < ncx_ else -1)
-            for d_ in deps_:
-                if d_ >= 0 and ncmd[d_]:
-                    best_c, best_k = max(best_c, int(depth_c[d_])), max(best_k, int(depth_k[d_]))
-            light_ = bool(cflags[rs] & abi.RECON_CTU_LIGHT)
-            depth_c[rs], depth_k[rs] = best_c + (0 if light_ else 1), best_k + (int(ncmd[rs]) + 3) // 4 if light_ else best_k + int(ncmd[rs])
-        recon_chain = {"ctus_with_commands": int(len(work.order)), "commands": int(len(work.cmds)),
-                       "longest_dependency_chain_ctus": int(depth_c.max()), "longest_dependency_chain_commands": int(depth_k.max()),
-                       "chain_note": "chains follow what the pass waits for (LIGHT CTUs: flagged luma neighbours only, weighted a quarter); tickets in vvc355_recon_order() order"}
+        # (statistics of `work` alone: computed once per run like `work` itself)
+        if ("recon_stats",) + wkey not in _GENERATED:
+            intra_samples = int(sum(int(c[3]) * int(c[4]) for c in work.cmds[work.cmds["kind"] == abi.RECON_MARK] if c[11] == 0)) * 3 // 2
+            # what bounds this stage is not bandwidth but the longest chain of dependent CTUs (left, upper-left, upper, upper-right
+            # neighbours that have commands), each walked by one wave per channel type: its length in CTUs and in commands
+            ncx_ = fr.ncx if hasattr(fr, "ncx") else (fr.width + CTB - 1) // CTB
+            ncmd = work.ctus["n_cmd"].astype(np.int64)
+            depth_c, depth_k = np.zeros(len(ncmd), np.int64), np.zeros(len(ncmd), np.int64)
+            cflags = work.ctus["flags"].astype(np.int64)
+            for rs in work.order:
+                rs = int(rs)
+                rx_, best_c, best_k = rs % ncx_, 0, 0
+                if cflags[rs] & abi.RECON_CTU_LIGHT:      # waits for the luma of the flagged neighbours only
+                    deps_ = ((rs - 1) if (rx_ and cflags[rs] & abi.RECON_CTU_LUMA_LEFT) else -1, (rs - ncx_) if cflags[rs] & abi.RECON_CTU_LUMA_UP else -1)
+                else:
+                    deps_ = ((rs - 1) if rx_ else -1, (rs - ncx_ - 1) if rx_ else -1, rs - ncx_, (rs - ncx_ + 1) if rx_ + 1 < ncx_ else -1)
+                for d_ in deps_:
+                    if d_ >= 0 and ncmd[d_]:
+                        best_c, best_k = max(best_c, int(depth_c[d_])), max(best_k, int(depth_k[d_]))
+                light_ = bool(cflags[rs] & abi.RECON_CTU_LIGHT)
+                depth_c[rs], depth_k[rs] = best_c + (0 if light_ else 1), best_k + (int(ncmd[rs]) + 3) // 4 if light_ else best_k + int(ncmd[rs])
+            recon_chain = {"ctus_with_commands": int(len(work.order)), "commands": int(len(work.cmds)),
+                           "longest_dependency_chain_ctus": int(depth_c.max()), "longest_dependency_chain_commands": int(depth_k.max()),
+                           "chain_note": "chains follow what the pass waits for (LIGHT CTUs: flagged luma neighbours only, weighted a quarter); tickets in vvc355_recon_order() order"}
+            _GENERATED[("recon_stats",) + wkey] = (intra_samples, recon_chain)
+        intra_samples, recon_chain = _GENERATED[("recon_stats",) + wkey]
         chain.append(Stage("intra_recon_wavefront", f"recon_wavefront_kernel<{bd}>", lambda st: lib.vvc355_recon_frame_pass(st, bd, ptr(d_rf), ctypes.addressof(rf)),
                            intra_samples * isz, writes=rec, check=check_recon))
         chain[-1].extra = {"bound": "dependency chain (one wave per CTU and channel type), not bandwidth", **recon_chain}
@@ -1356,6 +1367,45 @@ def self_check(width, height, bd, n_ctus=12, noise=False):
     return verify_step(lib, torch, frame, chain, n_ctus)
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_SAMPLES = (1 << 18, 1 << 16, 1 << 16)      # sampled positions per picture of Y, Cb, Cr (fewer when many pictures would exceed DUMP_BYTES)
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_outputs(path, torch, pictures):
+    """--dump-outputs DIR: the decoded pictures (ALF output planes) of the timed region's last step, in the order given, as arrays
+    that a run of another build with the same arguments can be compared with, file by file:
+
+        <C>_samples.npy              float32 [pictures, n]: component C (Y, Cb, Cr) at n positions drawn from a generator seeded with
+                                     DUMP_SEED (the same positions for every picture and every run at the same picture size)
+        <C>_row_sums.npy, _col_sums  float64 [pictures, rows] / [pictures, columns]: the exact sum of every row / column of C
+
+    The sums cover every sample of every picture, the samples locate a difference."""
+    n_pic = len(pictures)
+    dims = pictures[0].dims
+    sum_bytes = n_pic * sum(w + h for (w, h) in dims) * 8
+    want = [min(n, w * h) for n, (w, h) in zip(DUMP_SAMPLES, dims)]
+    room = DUMP_BYTES - (1 << 20) - sum_bytes
+    if room < 4 * n_pic * len(dims):
+        raise SystemExit(f"bench.py --dump-outputs: {n_pic} pictures of this size do not fit in {DUMP_BYTES >> 20} MB")
+    scale = min(1.0, room / (4 * n_pic * sum(want)))
+    os.makedirs(path, exist_ok=True)
+    for c, name in enumerate(("Y", "Cb", "Cr")):
+        w, h = dims[c]
+        n = max(1, int(want[c] * scale))
+        rng = np.random.default_rng(DUMP_SEED + c)
+        ys, xs = rng.integers(0, h, size=n), rng.integers(0, w, size=n)
+        planes = [p.out[c] for p in pictures]
+        idx = torch.from_numpy(ys * planes[0].stride(0) + xs).to(planes[0].device)
+        arrays = {
+            "samples": torch.stack([p.reshape(-1)[idx] for p in planes]).cpu().numpy().astype(np.float32),
+            "row_sums": torch.stack([p[:, :w].sum(dim=1, dtype=torch.int64) for p in planes]).cpu().numpy().astype(np.float64),
+            "col_sums": torch.stack([p[:, :w].sum(dim=0, dtype=torch.int64) for p in planes]).cpu().numpy().astype(np.float64),
+        }
+        for kind, a in arrays.items():
+            np.save(os.path.join(path, f"{name}_{kind}.npy"), a)
+
+
 def recorded_traffic(root, stage_name):
     """HBM bytes per launch from the committed rocprofv3 --pmc passes (profiles/pmc_traffic.json), or None."""
     path = os.path.join(root, "profiles", "pmc_traffic.json")
@@ -1699,19 +1749,19 @@ def parse_args(argv=None):
     ap.add_argument("--width", type=int, default=7680)
     ap.add_argument("--height", type=int, default=4320)
     ap.add_argument("--bd", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--gop", type=int, default=16, help="pictures per hierarchical-B group (a power of two): a step decodes one group of one stream, every picture "
                                                         "behind its two reference pictures; 0 = independent frames (--frames-in-flight)")
     ap.add_argument("--frames-in-flight", type=int, default=8, help="independent frames processed concurrently per step (one HIP stream each): the whole step with --gop 0, "
                                                                     "the secondary `independent_frames` figure otherwise; 1 = latency of a single frame")
-    ap.add_argument("--with-upload", action="store_true", help="--gop 0: additionally time the steps with every per-frame descriptor copied from pinned host memory first "
+    ap.add_argument("--with-upload", action="store_true", help="--full, --gop 0: additionally time the steps with every per-frame descriptor copied from pinned host memory first "
                                                                "(GOP mode always reports it: incl_descriptor_upload)")
-    ap.add_argument("--no-upload", action="store_true", help="GOP mode: skip the incl_descriptor_upload leg")
+    ap.add_argument("--no-upload", action="store_true", help="--full, GOP mode: skip the incl_descriptor_upload leg")
     ap.add_argument("--gop-check", type=int, default=0, metavar="GROUPS",
                     help="GOP mode, no timing: decode GROUPS groups with the concurrent scheduler (one stream per picture, event waits on the reference pictures), "
                          "again one picture at a time in decoding order on one stream, and once more serially in REVERSED order; prints how many decoded pictures "
                          "differ between the first two (must be 0) and between the last two (must not be 0: the pictures really read their references)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the untimed oracle check of one step (the `verified` object)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the untimed oracle check of one step (the `verified` object)")
     ap.add_argument("--verify-ctus", type=int, default=32, help="CTUs sampled for the prediction / transform stages of the oracle check")
     ap.add_argument("--no-lmcs", action="store_true", help="profiling aid: a picture without LMCS (no forward map on the inter prediction, no chroma residual scaling)")
     ap.add_argument("--noise", action="store_true", help="profiling aid: uniformly random reference samples and dense residuals (checkasm-style) "
@@ -1732,7 +1782,15 @@ def parse_args(argv=None):
     ap.add_argument("--stub-step-ms", type=float, default=None,
                     help="TEST AID: replace the GPU chain by a host sleep of this many ms per step (exercises the launcher, the rendezvous, "
                          "the barrier / max-over-ranks protocol and the JSON line on a machine without a GPU); the line says \"stub\": true")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: per-stage times and roofline, independent frames, the upload leg, "
+                         "the device copy rate, the oracle check (`verified`) and the CPU baseline (--no-verify / --no-cpu-baseline / --no-upload still drop legs)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the pictures decoded by the timed region's last step to DIR/<name>.npy (a fixed, seeded sample plus row and column sums)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main(argv=None):
@@ -1790,7 +1848,7 @@ def main(argv=None):
         order = gop_order(gop)
         objs = {(j, poc): Frame(torch, args.width, args.height, args.bd, seed=0x5EED0001 + rank + 977 * (j * gop + poc)) for j in range(n_sets) for poc in range(1, gop + 1)}
         for fr_i in objs.values():
-            fr_i.pin = not args.no_upload            # the per-frame arena's host twin is pinned: the upload leg copies from it
+            fr_i.pin = args.full and not args.no_upload          # the per-frame arena's host twin is pinned: the upload leg (--full) copies from it
 
         def ref_obj(j, poc):
             return objs[((j - 1) % n_sets, gop)] if poc == 0 else objs[(j, poc)]
@@ -1829,8 +1887,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     build_s = time.perf_counter() - t_build
 
-    # events are created before the timed region; inside it they are only recorded
-    pool = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in chain] for _ in range(args.steps)]
+    # events are created before the timed region; inside it they are only recorded (--full: the per-stage pass and the dominant stage)
+    pool = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in chain] for _ in range(args.steps)] if args.full else None
 
     def run_frame(f, events=None, step=0, only=None, stream=None):
         ts = stream if stream is not None else streams[f % len(streams)]
@@ -1954,37 +2012,39 @@ def main(argv=None):
     for _ in range(args.warmup):
         run_step()
     barrier()
-    recon_workgroups(0)
-    # Untimed pass of ONE frame alone with HIP events around every stage: the per-stage breakdown (`stages`), the latency of a frame
-    # and which stage dominates.  The timed region then carries events around that one stage only.
-    events = {}
-    t_lat = time.perf_counter()
-    for k in range(args.steps):
-        run_frame(0, events, k)
-    torch.cuda.synchronize()
-    frame_latency_ms = (time.perf_counter() - t_lat) / args.steps * 1e3
-    breakdown = {name: float(np.mean([a.elapsed_time(b) for a, b in ev])) for name, ev in events.items()}
-    # the in-order intra pass is a latency-bound dependent chain on a few hundred waves; with several frames in flight it runs
-    # beside the other frames' kernels, so the kernel that bounds throughput is the largest of the batched stages
-    throughput_stages = {k: v for k, v in breakdown.items() if k != "intra_recon_wavefront"} or breakdown
-    dom_name = max(throughput_stages, key=throughput_stages.get)
-    recon_workgroups(concurrent_wgs)
-    barrier()
-    # secondary figure: F mutually independent frames per step (in GOP mode: the odd pictures of one group) — the ceiling without
-    # reference dependencies
-    independent = None
-    if gop and not args.graph:
-        for _ in range(2):
-            run_independent()
+    breakdown, independent, dom_name = {}, None, None
+    if args.full:
+        recon_workgroups(0)
+        # Untimed pass of ONE frame alone with HIP events around every stage: the per-stage breakdown (`stages`), the latency of a frame
+        # and which stage dominates.  The timed region then carries events around that one stage only.
+        events = {}
+        t_lat = time.perf_counter()
+        for k in range(args.steps):
+            run_frame(0, events, k)
         torch.cuda.synchronize()
-        t_i = time.perf_counter()
-        n_i = max(4, args.steps // 2)
-        for _ in range(n_i):
-            run_independent()
-        torch.cuda.synchronize()
-        el_i = sharding.max_over_ranks(dist, torch, world, time.perf_counter() - t_i, "cpu")
-        independent = {"value": world * n_ff * n_i / el_i, "unit": "frames/s", "frames_in_flight": n_ff, "steps": n_i,
-                       "note": "mutually independent frames (the odd pictures of one group), one HIP stream each, no reference waits: not a decode rate"}
+        frame_latency_ms = (time.perf_counter() - t_lat) / args.steps * 1e3
+        breakdown = {name: float(np.mean([a.elapsed_time(b) for a, b in ev])) for name, ev in events.items()}
+        # the in-order intra pass is a latency-bound dependent chain on a few hundred waves; with several frames in flight it runs
+        # beside the other frames' kernels, so the kernel that bounds throughput is the largest of the batched stages
+        throughput_stages = {k: v for k, v in breakdown.items() if k != "intra_recon_wavefront"} or breakdown
+        dom_name = max(throughput_stages, key=throughput_stages.get)
+        recon_workgroups(concurrent_wgs)
+        barrier()
+        # secondary figure: F mutually independent frames per step (in GOP mode: the odd pictures of one group) — the ceiling without
+        # reference dependencies
+        independent = None
+        if gop and not args.graph:
+            for _ in range(2):
+                run_independent()
+            torch.cuda.synchronize()
+            t_i = time.perf_counter()
+            n_i = max(4, args.steps // 2)
+            for _ in range(n_i):
+                run_independent()
+            torch.cuda.synchronize()
+            el_i = sharding.max_over_ranks(dist, torch, world, time.perf_counter() - t_i, "cpu")
+            independent = {"value": world * n_ff * n_i / el_i, "unit": "frames/s", "frames_in_flight": n_ff, "steps": n_i,
+                           "note": "mutually independent frames (the odd pictures of one group), one HIP stream each, no reference waits: not a decode rate"}
     barrier()
     events = {}
     if args.graph:
@@ -2013,17 +2073,22 @@ def main(argv=None):
     else:
         t0 = time.perf_counter()
         for k in range(args.steps):
-            run_step(events, k, only=dom_name)
+            run_step(events if args.full else None, k, only=dom_name)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
     barrier()
     elapsed = sharding.max_over_ranks(dist, torch, world, elapsed, "cpu")
+    if args.dump_outputs and rank == 0:
+        # what the last timed step decoded, before any later leg touches the pictures: the group's pictures in POC order (GOP mode),
+        # else the frames in flight
+        last = [objs[((gop_k[0] - 1) % n_sets, poc)] for poc in range(1, gop + 1)] if gop and not args.graph else frames
+        dump_outputs(args.dump_outputs, torch, last)
 
     # second figure: the same frames with every per-frame descriptor (job arrays, side tables, command lists) copied from pinned host
     # memory at the start of each frame — what a decoder that builds them on the host pays over PCIe (the coefficient levels, which
     # are generated on the device here, are not included: their size is reported).  Measured on the F independent frames.
     upload = None
-    if gop and not args.graph and not args.no_upload:
+    if args.full and gop and not args.graph and not args.no_upload:
         for key, fr_i in objs.items():
             lo_, hi_ = fr_i.arena.data_ptr(), fr_i.arena.data_ptr() + fr_i.arena.numel()
             pinned_of[key] = [(fr_i.arena[:fr_i.arena_used], fr_i.arena_host[:fr_i.arena_used])]          # one copy: the picture's arena
@@ -2056,7 +2121,7 @@ def main(argv=None):
                   "what": "the same groups of pictures with every picture's per-frame tables, records and descriptor arrays copied from pinned host memory "
                           "first — on a copy stream, as soon as the picture object is free; the picture's own stream waits for the copy's event",
                   "not_included": "coefficient levels (int32 in the reference ABI, generated on the device here)"}
-    elif args.with_upload and not args.graph:
+    elif args.full and args.with_upload and not args.graph:
         pinned = [[(frames[f].torch_of[p_], torch.from_numpy(h_).pin_memory()) for p_, h_ in frames[f].host.items()] for f in range(n_ff)]
         up_bytes = sum(h_.nbytes for h_ in frames[0].host.values())
 
@@ -2078,19 +2143,6 @@ def main(argv=None):
                   "not_included": "coefficient levels (int32 in the reference ABI, generated on the device here)"}
 
     if rank == 0:
-        stages = {}
-        kernel_ms_total = sum(breakdown.values())
-        for st in chain:
-            gbs = st.algorithmic_bytes / (breakdown[st.name] * 1e-3) / 1e9
-            stages[st.name] = {"kernel": st.kernel, "ms": breakdown[st.name], "algorithmic_bytes": st.algorithmic_bytes,
-                               "GB/s": gbs, "frac_of_hbm_peak": gbs / HBM_PEAK_GBS, "share_of_frame_kernel_time": breakdown[st.name] / kernel_ms_total}
-            if getattr(st, "extra", None):
-                stages[st.name].update(st.extra)
-                if "longest_dependency_chain_commands" in st.extra:
-                    stages[st.name]["us_per_command_on_the_chain"] = breakdown[st.name] * 1e3 / max(1, st.extra["longest_dependency_chain_commands"])
-        dom = next(st for st in chain if st.name == dom_name)         # the batched stage with the largest launch time
-        in_region = float(np.mean([a.elapsed_time(b) for a, b in events[dom_name]])) if events.get(dom_name) else None
-        recon_ms = breakdown.get("intra_recon_wavefront")
         if gop:
             work = (f"one hierarchical-B group of {gop} pictures of one stream per step (decode order {' '.join(str(p_) for p_, _l, _h in order)}; every picture's inter "
                     f"prediction reads the decoded output of its two reference pictures and starts behind their ALF stage; consecutive groups overlap; "
@@ -2101,8 +2153,6 @@ def main(argv=None):
             par = f"{n_ff} frame(s) in flight per GPU, one HIP stream each"
         out = {
             "metric": "decoded frames/sec (4K/8K 10-bit VVC) per GPU",
-            "parity": "device output == in-repo CPU oracle on this frame (`verified`: sampled CTUs per prediction / transform stage, whole picture "
-                      "for the loop-filter stages); the oracle itself is unpinned (no FATE bitstreams or reference build in this environment)",
             "value": world * frames_per_step * args.steps / elapsed,
             "unit": "frames/s",
             "n_gpus": world,
@@ -2110,9 +2160,6 @@ def main(argv=None):
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
             "frames_per_step": frames_per_step,
-            "frame_latency_ms": frame_latency_ms,          # one frame alone, stage after stage (untimed pass): latency, not throughput
-            "independent_frames": independent,             # the same frames without reference dependencies: a ceiling, not a decode rate
-            "incl_descriptor_upload": upload,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -2126,9 +2173,31 @@ def main(argv=None):
                             f"stages per picture: {', '.join(st.name for st in chain)}",
                 "not_yet_in_chain": MISSING + ([] if MC_TOOLS == 3 and not args.only and AFFINE_FRAC == 0.06 and INTER_FRAC == 0.8 and SAO_TABLES and ALF_TABLES and not DEBLOCK_JOBS and not args.graph and not args.noise else ["PROFILING RUN: --noise / --graph / --mc-tools / --only / --affine-frac / --inter-frac / --sao-jobs / --alf-jobs / --deblock-jobs change the workload; not the metric"]),
                 "parallelism": f"{world} independent stream(s), one per GPU, no collective; {par}, GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')}; in-order pass: "
-                               f"{concurrent_wgs or 192} persistent workgroups per picture in the timed region, 192 for the one-picture legs (`stages`, frame_latency_ms)",
+                               f"{concurrent_wgs or 192} persistent workgroups per picture in the timed region"
+                               + (", 192 for the one-picture legs (`stages`, frame_latency_ms)" if args.full else ""),
                 "frame_objects_built": len(objs) if gop else n_ff, "build_s": round(build_s, 1),
             },
+        }
+    if rank == 0 and args.full:
+        stages = {}
+        kernel_ms_total = sum(breakdown.values())
+        for st in chain:
+            gbs = st.algorithmic_bytes / (breakdown[st.name] * 1e-3) / 1e9
+            stages[st.name] = {"kernel": st.kernel, "ms": breakdown[st.name], "algorithmic_bytes": st.algorithmic_bytes,
+                               "GB/s": gbs, "frac_of_hbm_peak": gbs / HBM_PEAK_GBS, "share_of_frame_kernel_time": breakdown[st.name] / kernel_ms_total}
+            if getattr(st, "extra", None):
+                stages[st.name].update(st.extra)
+                if "longest_dependency_chain_commands" in st.extra:
+                    stages[st.name]["us_per_command_on_the_chain"] = breakdown[st.name] * 1e3 / max(1, st.extra["longest_dependency_chain_commands"])
+        dom = next(st for st in chain if st.name == dom_name)         # the batched stage with the largest launch time
+        in_region = float(np.mean([a.elapsed_time(b) for a, b in events[dom_name]])) if events.get(dom_name) else None
+        recon_ms = breakdown.get("intra_recon_wavefront")
+        out.update({
+            "parity": "device output == in-repo CPU oracle on this frame (`verified`: sampled CTUs per prediction / transform stage, whole picture "
+                      "for the loop-filter stages); the oracle itself is unpinned (no FATE bitstreams or reference build in this environment)",
+            "frame_latency_ms": frame_latency_ms,          # one frame alone, stage after stage (untimed pass): latency, not throughput
+            "independent_frames": independent,             # the same frames without reference dependencies: a ceiling, not a decode rate
+            "incl_descriptor_upload": upload,
             "roofline": {
                 "stage": dom.name,
                 "kernel": dom.kernel,
@@ -2155,7 +2224,7 @@ def main(argv=None):
                              "valu": recorded_valu(ROOT, dom.name)},
             },
             "stages": stages,
-        }
+        })
         # what a plain device-to-device copy reaches on this box (report the practical peak beside the vendor figure)
         n_copy = 1 << 28
         a_buf = torch.empty(n_copy, dtype=torch.uint8, device="cuda")
@@ -2173,6 +2242,7 @@ def main(argv=None):
             out["verified"] = verify_step(lib, torch, frame, chain, args.verify_ctus)
         if not args.no_cpu_baseline and world == 1:       # a reported baseline, timed once: rank 0 of the single-GPU run
             out["cpu_baseline"] = cpu_baseline(ROOT, frame, args.cpu_seconds, args.cpu_workers)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

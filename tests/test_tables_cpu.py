@@ -4,9 +4,9 @@ libavcodec/vvc/vvc_data.c and the inline tables of vvc_filter.c, vvc_intra.c, vv
 (Table 43, the intra angles, the level scale, the filtered modes and filter thresholds, CCLM's divSigTable, ALF's varTab and
 transpose index lists, the 4x4 diagonal scan) as data.  Where a kernel uses a packed or arithmetic form of such a table
 (intra.hip, itx.hip, alf.hip) a static_assert proves it equal to the exported initialiser at compile time.
-Where the reference is present (the build container) the values are compared one by one and the committed digests are checked to
-be current; everywhere (the GPU box has no reference) the library's tables are compared with the committed digests
-(tests/golden/tables_sha256.json).  The DCT-2 table has no counterpart in vvc_data.c (the reference hard-codes DCT-2 butterflies in
+The values tools/ref_tables.py read out of the reference are committed as data (tests/golden/tables_values.npz): the library's
+tables are compared with them one by one, the committed digests (tests/golden/tables_sha256.json) are checked to be those of the
+same values, and the library's tables are compared with the digests.  The DCT-2 table has no counterpart in vvc_data.c (the reference hard-codes DCT-2 butterflies in
 vvc_itx_1d.c); it is checked against the closed form round(64 * sqrt(2) * cos(j * pi / 128))-style magnitudes through the
 transform tests instead (tests/test_oracle_cpu.py, tests/test_itx_gpu.py)."""
 import ctypes
@@ -48,14 +48,13 @@ def test_library_table_matches_committed_digest(lib, name):
     assert ref_tables.digest(FMT[meta["type"]], got) == meta["sha256"], f"vvc355_tab_{name} differs from the reference's table"
 
 
-@pytest.mark.skipif(not os.path.exists(ref_tables.REF), reason="the reference tree is only present in the build container")
 def test_against_reference_values_and_fixture_current(lib):
-    ref = ref_tables.read_reference()
+    ref = ref_tables.read_values()
     fix = fixture()
     assert sorted(ref) == sorted(fix)
     for name, (fmt, want) in ref.items():
         meta = fix[name]
-        assert meta["count"] == len(want) and meta["sha256"] == ref_tables.digest(fmt, want), f"tests/golden/tables_sha256.json is stale for {name}"
+        assert meta["count"] == len(want) and meta["sha256"] == ref_tables.digest(fmt, want), f"tests/golden/tables_sha256.json and tables_values.npz disagree for {name}"
         got = exported(lib, name, meta)
         bad = [i for i, (a, b) in enumerate(zip(got, want)) if a != b]
         assert not bad, f"vvc355_tab_{name}: {len(bad)} entries differ from vvc_data.c, first at {bad[0]}: {got[bad[0]]} != {want[bad[0]]}"

@@ -3,9 +3,9 @@
 profiles/pmc_traffic.json: HBM bytes per stage per step (= per launch of the stage), which bench.py reports as
 roofline.traffic.
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    python3 tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write 4 > profiles/pmc_traffic.json
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d <fetch dir> -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d <write dir> -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    python3 tools/pmc_traffic.py <fetch dir> <write dir> 4 > profiles/pmc_traffic.json
 
 Units and the gfx950 correction follow /opt/skills/guides/MI355X_MICROARCH.md (HBM section): both counters are in KiB;
 FETCH_SIZE tallies 128-byte requests as 64 bytes, so read bytes = 2 x FETCH_SIZE; WRITE_SIZE is exact.

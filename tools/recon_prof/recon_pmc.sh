@@ -3,7 +3,7 @@ cd ${GRAFT_REPO_ROOT:-$PWD}
 export TMPDIR=/tmp
 O=$PWD/gpurun_out/recon_pmc
 rm -rf $O; mkdir -p $O
-B="python3 bench.py --only intra_recon_wavefront --gop 0 --frames-in-flight 1 --steps 2 --warmup 1 --no-verify --no-cpu-baseline $EXTRA"
+B="python3 bench.py --full --only intra_recon_wavefront --gop 0 --frames-in-flight 1 --steps 2 --warmup 1 --no-verify --no-cpu-baseline $EXTRA"
 i=0
 for set in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH" "SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA" "SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_MISC SQ_INST_LEVEL_LDS"; do
   i=$((i+1))

@@ -5,7 +5,7 @@ sys.path.insert(0, ROOT)
 from ffvvc_amd import abi
 abi.LIB_PATH = os.path.join(ROOT, "tools", "recon_prof", "libvvc_mi355_prof.so")
 import bench
-bench.main(["--only", "intra_recon_wavefront", "--gop", "0", "--frames-in-flight", "1", "--steps", "3", "--warmup", "1", "--no-verify", "--no-cpu-baseline"] + sys.argv[1:])
+bench.main(["--full", "--only", "intra_recon_wavefront", "--gop", "0", "--frames-in-flight", "1", "--steps", "3", "--warmup", "1", "--no-verify", "--no-cpu-baseline"] + sys.argv[1:])
 lib = abi.load()
 buf = (ctypes.c_ulonglong * (4096 * 8))()
 lib.vvc355_recon_prof_read.argtypes = [ctypes.c_void_p, ctypes.c_int]

@@ -12,6 +12,8 @@ import struct
 
 REF = "/root/reference/libavcodec/vvc/vvc_data.c"
 FIXTURE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "tables_sha256.json")
+VALUES = os.path.join(os.path.dirname(FIXTURE), "tables_values.npz")     # the values themselves, one array per table (data, not source)
+NP_TYPE = {"b": "int8", "B": "uint8", "h": "int16", "H": "uint16"}
 
 
 def _strip(text):
@@ -119,13 +121,23 @@ def digest(fmt, values):
     return hashlib.sha256(struct.pack("<%d%s" % (len(values), fmt), *values)).hexdigest()
 
 
+def read_values(path=VALUES):
+    """The committed copy of read_reference()'s output: {name: (struct format, values)}."""
+    import numpy as np
+    fmt_of = {v: k for k, v in NP_TYPE.items()}
+    with np.load(path) as z:
+        return {name: (fmt_of[str(z[name].dtype)], [int(v) for v in z[name]]) for name in z.files}
+
+
 def main():
+    import numpy as np
     t = read_reference()
+    np.savez_compressed(VALUES, **{name: np.array(v, dtype=NP_TYPE[fmt]) for name, (fmt, v) in sorted(t.items())})
     fix = {name: {"type": {"b": "int8", "B": "uint8", "h": "int16", "H": "uint16"}[fmt], "count": len(v), "sha256": digest(fmt, v)} for name, (fmt, v) in sorted(t.items())}
     with open(FIXTURE, "w") as f:
         json.dump({"source": "libavcodec/vvc/vvc_data.c, vvc_filter.c, vvc_intra.c, vvc_intra_template.c, vvc_filter_template.c of the reference, read by tools/ref_tables.py", "tables": fix}, f, indent=1)
         f.write("\n")
-    print("wrote", FIXTURE, len(fix), "tables")
+    print("wrote", FIXTURE, "and", VALUES, len(fix), "tables")
 
 
 if __name__ == "__main__":
