@@ -70,6 +70,32 @@ __device__ __forceinline__ Taps8 make_taps8(uint32_t lo, uint32_t hi)
     return t;
 }
 
+// vvc_inter.c:642-681
+__device__ __forceinline__ int parametric_mv_refine(int sad_minus, int sad_center, int sad_plus)
+{
+    int denom = ((sad_minus + sad_plus) - (sad_center << 1)) << 3;
+    if (!denom)
+        return 0;
+    if (sad_minus == sad_center)
+        return -8;
+    if (sad_plus == sad_center)
+        return 8;
+    int num = (sad_minus - sad_plus) * 16, quotient = 0;
+    const bool neg = num < 0;
+    if (neg)
+        num = -num;
+#pragma unroll
+    for (int counter = 0; counter < 3; counter++) {
+        quotient <<= 1;
+        if (num >= denom) {
+            num -= denom;
+            quotient++;
+        }
+        denom >>= 1;
+    }
+    return neg ? -quotient : quotient;
+}
+
 template <int BD, int W, int H>
 __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, ToolsLds<W, H> &L, int lane)
 {

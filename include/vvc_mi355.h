@@ -534,6 +534,10 @@ void vvc355_pred_fused_batch(void *stream, int bd, const vvc355_pred_job *jobs_d
  *   weight_flag, denom, w0, w1, o0, o1   what derive_weight (:137-167) returns for this component
  *   pred_flag    uni-predicted blocks (luma_mc_uni :222-251 / chroma_mc_uni :298-328: put_uni / put_uni_w, no DMVR / BDOF) go through
  *                the same entry with pred_flag 1 or 2; their weights are derive_weight_uni's (denom, w0 = wx, o0 = ox)
+ *   dmvr, bdof   on luma they act only on bi-predicted sub-blocks of 8 or 16 samples per side (the only ones VVC applies them to:
+ *                coding units of at least 8x8 and 128 samples, sub-blocks of min(cb, 16) per side).  On any other luma job they are
+ *                ignored: plain bi-prediction, and *rec gets the unrefined motion with bdof 0.  On chroma, dmvr selects the
+ *                clamp window (above) and bdof is ignored.
  * Launch the luma jobs of a frame first, then the chroma jobs that point at their records.
  */
 typedef struct vvc355_bipred_job {

@@ -254,3 +254,60 @@ def test_bdof_rightmost_subblock(dev, orc, bd):
     # the case is not vacuous: the right-most sub-blocks are not plain averages
     avg = ((refs[0].astype(np.int64) + refs[1] + 1) >> 1)
     assert any(np.any(want[y:y + 16, x + 12:x + 16] != avg[y:y + 16, x + 12:x + 16]) for (x, y) in blocks)
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_bipred_tools_flags_outside_contract(dev, orc, bd):
+    """dmvr / bdof on a luma job that is not a bi-predicted sub-block of 8 or 16 on a side (include/vvc_mi355.h, vvc355_bipred_job):
+    the flags are ignored — plain bi-prediction, and the record holds the unrefined motion with bdof, min_sad and searched 0.
+    VVC never produces such jobs; the expectation is the oracle's block with both flags cleared."""
+    bc.bind_oracle(orc)
+    rng = np.random.default_rng(0x5EED0C00 + bd)
+    pw, ph, isz = 128, 64, 1 if bd == 8 else 2
+    refs = [bc.smooth_picture(rng, ph, pw, bd) for _ in range(2)]
+    want = np.full((ph, pw), 0x21, refs[0].dtype)
+    d_refs = [batch.DeviceBuffer.from_host(r) for r in refs]
+    d_out = batch.DeviceBuffer.from_host(want)
+    # (w, h, pred_flag): bi-predicted shapes outside {8, 16}^2, and uni-predicted ones (the flags need both lists)
+    shapes = [(4, 8, 3), (16, 4, 3), (8, 4, 3), (4, 16, 3), (16, 12, 3), (8, 12, 3), (4, 4, 3), (16, 16, 1), (8, 8, 2)]
+    flags = [(1, 1), (1, 0), (0, 1)]
+    n = len(shapes) * len(flags)
+    want_rec = (abi.BipredResult * n)()
+    d_rec = batch.DeviceBuffer.from_host(np.full(n * 32, 0x5A, np.uint8))       # every field must be written
+    lut = np.sort(np.random.default_rng(0x10C5 + bd).integers(0, 1 << bd, size=1 << bd)).astype(refs[0].dtype)
+    d_lut = batch.DeviceBuffer.from_host(lut)
+    arr = (abi.BipredJob * n)()
+    for i in range(n):
+        (w, h, pred_flag), (dmvr, bdof) = shapes[i % len(shapes)], flags[i // len(shapes)]
+        x, y = 16 * (i % 8), 16 * (i // 8)
+        j = abi.BipredJob()
+        j.x, j.y, j.w, j.h, j.pic_w, j.pic_h, j.dmvr, j.bdof = x, y, w, h, pw, ph, dmvr, bdof
+        mv = [int(v) for v in rng.integers(-200, 201, size=4)] if i % 4 else [int(v) for v in rng.integers(-3000, 3001, size=4)]
+        for k, v in enumerate(mv):
+            j.mv[k] = v
+        j.pred_flag = pred_flag
+        j.weight_flag = int(i % 5 == 0)
+        j.denom = int(rng.integers(0, 8))
+        j.w0, j.w1, j.o0, j.o1 = (int(v) for v in rng.integers(-128, 128, size=4))
+        j.dst_stride = j.ref0_stride = j.ref1_stride = pw * isz
+        hj = abi.BipredJob.from_buffer_copy(j)
+        hj.dmvr = hj.bdof = 0
+        hj.dst, hj.ref0, hj.ref1 = P(want, y * pw + x), P(refs[0]), P(refs[1])
+        hj.rec = ctypes.addressof(want_rec[i])
+        hj.lmcs_lut = P(lut) if i % 3 == 0 else 0
+        orc.orc_bipred_block(bd, ctypes.byref(hj))
+        j.dst, j.ref0, j.ref1 = d_out.ptr + (y * pw + x) * isz, d_refs[0].ptr, d_refs[1].ptr
+        j.rec = d_rec.ptr + 32 * i
+        j.lmcs_lut = d_lut.ptr if i % 3 == 0 else 0
+        arr[i] = j
+    d_jobs = batch.jobs_to_device(arr)
+    dev.vvc355_bipred_batch(None, bd, d_jobs.ptr, n)
+    dev.vvc355_stream_sync(None)
+    got = d_out.to_host(want.dtype, want.shape)
+    bad = np.argwhere(got != want)
+    assert len(bad) == 0, f"{len(bad)} samples differ, first at {bad[0].tolist()}"
+    got_rec = d_rec.to_host(np.int32, (n, 8))
+    exp_rec = np.frombuffer(bytes(want_rec), np.int32).reshape(n, 8)
+    bad = np.argwhere(got_rec[:, :7] != exp_rec[:, :7])
+    assert len(bad) == 0, f"record {bad[0][0]}: got {got_rec[bad[0][0]].tolist()} want {exp_rec[bad[0][0]].tolist()}"
+    assert np.all(exp_rec[:, 4] == 0) and np.any(want != 0x21)
