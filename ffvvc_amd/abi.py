@@ -128,6 +128,11 @@ BATCH_SIGNATURES = {
     "gpm_batch":        ("v", "pipi"),
     "inter_frame_build": ("v", "ppp"),
     "inter_frame_pass": ("v", "pipp"),
+    "affine_frame_build": ("v", "ppp"),
+    "affine_frame_pass": ("v", "pipp"),
+    "gpm_frame_build":  ("v", "ppp"),
+    "gpm_frame_pass":   ("v", "pipp"),
+    "gpm_weights":      ("v", "iiiiip"),
     "deblock_frame_pass": ("v", "pipp"),
     "sao_frame_pass":   ("v", "pipp"),
     "alf_frame_pass":   ("v", "pippp"),
@@ -342,6 +347,24 @@ class InterFrame(ctypes.Structure):
                 ("pad_", ctypes.c_uint8 * 4), ("lmcs_fwd_lut", ctypes.c_uint64)]
 
 
+class AffineCu(ctypes.Structure):
+    """Mirror of vvc355_affine_cu."""
+    _fields_ = [("x0", ctypes.c_int16), ("y0", ctypes.c_int16), ("cb_width", ctypes.c_int16), ("cb_height", ctypes.c_int16),
+                ("num_sb_x", ctypes.c_uint8), ("num_sb_y", ctypes.c_uint8), ("prof_flags", ctypes.c_uint8), ("slice", ctypes.c_uint8),
+                ("first_job", ctypes.c_uint32), ("diff_mv", ctypes.c_int16 * 16 * 2 * 2)]
+
+
+class AffineFrame(ctypes.Structure):
+    """Mirror of vvc355_affine_frame."""
+    _fields_ = [("pic", InterFrame), ("cus", ctypes.c_uint64), ("jobs_luma", ctypes.c_uint64), ("jobs_chroma", ctypes.c_uint64),
+                ("n_cus", ctypes.c_int32), ("n_jobs", ctypes.c_int32)]
+
+
+class GpmFrame(ctypes.Structure):
+    """Mirror of vvc355_gpm_frame."""
+    _fields_ = [("pic", InterFrame), ("cus", ctypes.c_uint64), ("jobs", ctypes.c_uint64), ("n_cus", ctypes.c_int32), ("n_jobs", ctypes.c_int32)]
+
+
 class GpmJob(ctypes.Structure):
     """Mirror of vvc355_gpm_job (and of the oracle's orc_gpm_job)."""
     _fields_ = [("base", BipredJob), ("weights", ctypes.c_uint64), ("step_x", ctypes.c_int32), ("step_y", ctypes.c_int32)]
@@ -399,6 +422,13 @@ class MvField(ctypes.Structure):
     """Mirror of vvc355_mvfield (= the reference's MvField, vvc_ctu.h:195-202)."""
     _fields_ = [("mv", (ctypes.c_int32 * 2) * 2), ("ref_idx", ctypes.c_int8 * 2), ("hpel_if_idx", ctypes.c_uint8),
                 ("bcw_idx", ctypes.c_uint8), ("pred_flag", ctypes.c_uint8), ("ciip_flag", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 2)]
+
+
+class GpmCu(ctypes.Structure):
+    """Mirror of vvc355_gpm_cu (gpm_mv: two MvField)."""
+    _fields_ = [("x0", ctypes.c_int16), ("y0", ctypes.c_int16), ("cb_width", ctypes.c_int16), ("cb_height", ctypes.c_int16),
+                ("partition_idx", ctypes.c_uint8), ("slice", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 2), ("first_job", ctypes.c_uint32),
+                ("gpm_mv", MvField * 2)]
 
 
 class BsFrame(ctypes.Structure):

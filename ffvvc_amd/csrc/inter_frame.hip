@@ -3,13 +3,11 @@
 // mc_fused.hip.  Reference behaviour: pred_regular_blk and its helpers, libavcodec/vvc/vvc_inter.c:129-177 (derive_weight_uni,
 // derive_weight), :764-813 (derive_sb_mv, the sub-block walk), pred_regular_luma / _chroma (:549-640: filter set, uni / bi split).
 #include "common.hpp"
+#include "inter_weight.hpp"
 #include "runtime.hpp"
 #include "../../include/vvc_mi355.h"
 
 namespace vvc355 {
-
-struct MvFieldDev { int32_t mv[2][2]; int8_t ref_idx[2]; uint8_t hpel_if_idx, bcw_idx, pred_flag, ciip_flag, pad_[2]; };
-static_assert(sizeof(MvFieldDev) == 24, "MvField layout (vvc_ctu.h:195-202)");
 
 // one thread per coding unit: its sub-blocks, each in 16x16 tiles, one luma and two chroma jobs per tile
 __global__ __launch_bounds__(256) void inter_build_kernel(const vvc355_inter_frame *__restrict__ fp)
@@ -26,7 +24,6 @@ __global__ __launch_bounds__(256) void inter_build_kernel(const vvc355_inter_fra
     vvc355_bipred_result *rec = (vvc355_bipred_result *)f.records;
     const int sbw = pu.cb_width / pu.num_sb_x, sbh = pu.cb_height / pu.num_sb_y;
     const int tw = min(sbw, 16), th = min(sbh, 16);
-    const int bcw_w_lut[5] = { 4, 5, 3, 10, -2 };                       // vvc_inter.c:29
     uint32_t job = pu.first_job;
     for (int sby = 0; sby < pu.num_sb_y; sby++)
         for (int sbx = 0; sbx < pu.num_sb_x; sbx++) {
@@ -60,27 +57,7 @@ __global__ __launch_bounds__(256) void inter_build_kernel(const vvc355_inter_fra
                         j.pred_flag = mv.pred_flag;
                         // predict_inter's lmcs.filter (:888-891): luma of the coding unit goes through the forward map, CIIP units excepted
                         j.lmcs_lut = (!c && sl->lmcs_used && !pu.ciip_flag) ? f.lmcs_fwd_lut : 0;
-                        if (bi) {
-                            // derive_weight (:149-177)
-                            const int weight_flag = sl->weighted_pred || (sl->weighted_bipred && !pu.dmvr_flag);
-                            if ((weight_flag || mv.bcw_idx) && !(mv.bcw_idx && pu.ciip_flag)) {
-                                j.weight_flag = 1;
-                                if (mv.bcw_idx) {
-                                    j.denom = 2; j.w1 = (int16_t)bcw_w_lut[mv.bcw_idx]; j.w0 = (int16_t)(8 - j.w1);
-                                } else {
-                                    j.denom = sl->log2_denom[c > 0];
-                                    j.w0 = sl->weight[0][c][mv.ref_idx[0]]; j.w1 = sl->weight[1][c][mv.ref_idx[1]];
-                                    j.o0 = sl->offset[0][c][mv.ref_idx[0]]; j.o1 = sl->offset[1][c][mv.ref_idx[1]];
-                                }
-                            }
-                        } else if (sl->weighted_pred || sl->weighted_bipred) {
-                            // derive_weight_uni (:129-146)
-                            const int lx = mv.pred_flag - 1;
-                            j.weight_flag = 1;
-                            j.denom = sl->log2_denom[c > 0];
-                            j.w0 = sl->weight[lx][c][mv.ref_idx[lx]];
-                            j.o0 = sl->offset[lx][c][mv.ref_idx[lx]];
-                        }
+                        set_pred_weight(j, derive_pred_weight(sl, mv, c, pu.dmvr_flag, pu.ciip_flag));
                         if (c == 0) jl[job] = j; else jc[2 * job + c - 1] = j;
                     }
                 }

@@ -75,6 +75,9 @@ extern const uint8_t vvc355_tab_cclm_div_sig[16];                     /* div_sig
 extern const uint8_t vvc355_tab_alf_arg_var[16];                      /* arg_var[], vvc_filter_template.c:272 */
 extern const uint8_t vvc355_tab_alf_transpose_index[48];              /* index[4][12], vvc_filter_template.c:387 */
 extern const uint8_t vvc355_tab_diag_scan_4x4_x[16], vvc355_tab_diag_scan_4x4_y[16];      /* ff_vvc_diag_scan_x / _y [2][2], vvc_data.c:27,152 */
+extern const uint8_t vvc355_tab_gpm_angle_idx[64];                    /* ff_vvc_gpm_angle_idx, vvc_data.c:1998 (partition -> angleIdx) */
+extern const uint8_t vvc355_tab_gpm_distance_idx[64];                 /* ff_vvc_gpm_distance_idx, vvc_data.c:2005 (partition -> distanceIdx) */
+extern const int8_t  vvc355_tab_gpm_distance_lut[32];                 /* ff_vvc_gpm_distance_lut, vvc_data.c:2012 (disLut) */
 
 /* ------------------------------------------------------------------ ALF (alf.hip) */
 
@@ -641,6 +644,68 @@ typedef struct vvc355_inter_frame {
 void vvc355_inter_frame_build(void *stream, const vvc355_inter_frame *frame_dev, const vvc355_inter_frame *frame_host);
 /* build + luma + chroma */
 void vvc355_inter_frame_pass(void *stream, int bd, const vvc355_inter_frame *frame_dev, const vvc355_inter_frame *frame_host);
+
+/* ------------------------------------------------------------------ affine and geometric-partition stage drivers (inter_cu.hip) */
+
+/*
+ * The other two branches of predict_inter (vvc_inter.c:875-891) for a whole picture, from the same decoder tables as
+ * vvc355_inter_frame_pass plus one small record per coding unit:
+ *   affine (pu->inter_affine_flag)  pred_affine_blk (:828-873): one vvc355_affine_job per 4x4 luma sub-block, motion / ref_idx /
+ *          bcw_idx / pred_flag from the MvField table, PROF switches and offsets from the record, weights of derive_weight_uni /
+ *          derive_weight (dmvr_flag 0); chroma per (1 << hs) x (1 << vs) sub-blocks, 4x4 chroma samples at the averaged motion of
+ *          derive_affine_mvc (:813-826) as vvc355_bipred_job pairs (Cb, Cr) with filter set 0 and rec = 0.  Then vvc355_affine_batch
+ *          and vvc355_bipred_chroma_batch.
+ *   GPM (pu->merge_gpm_flag)  pred_gpm_blk (:466-527): per present component the coding unit in <= 16x16 tiles, one vvc355_gpm_job
+ *          each, part 0 / part 1 from the record's gpm_mv, weights addressed in the library's own masks (computed from the standard's
+ *          closed form; vvc355_gpm_weights shows them).  Then vvc355_gpm_batch.
+ * The picture is described by an embedded vvc355_inter_frame: the one descriptor a decoder fills for the regular pass serves all three
+ * drivers by copy, and the host copy that _pass reads (chroma_format_idc, the counts) is self-contained, which a pointer to a device
+ * descriptor would not be.  Of it only dst, dst_stride, mvf, mvf_stride, refs, slices, width, height, hs, vs, chroma_format_idc,
+ * pixel_shift and lmcs_fwd_lut are read; pus, jobs_luma, jobs_chroma, records, dmvr_mvf, n_pus and n_jobs are ignored.
+ * Affine and GPM coding units are never CIIP; LMCS applies to their luma where the slice has lmcs_used.
+ */
+typedef struct vvc355_affine_cu {
+    int16_t  x0, y0, cb_width, cb_height;     /* luma samples */
+    uint8_t  num_sb_x, num_sb_y;              /* cb_width >> 2, cb_height >> 2 (affine sub-blocks are 4x4, vvc_mvs.c:1272); other values are
+                                               * rejected: the coding unit's jobs then predict nothing (pred_flag 0) */
+    uint8_t  prof_flags;                      /* bit l = pu->cb_prof_flag[l] */
+    uint8_t  slice;                           /* index into frame.slices[] */
+    uint32_t first_job;                       /* running sum of num_sb_x * num_sb_y */
+    int16_t  diff_mv[2][2][16];               /* [list][x | y][16]: pu->diff_mv_x / _y (vvc_mvs.c:361-376); the jobs point here */
+} vvc355_affine_cu;
+typedef struct vvc355_affine_frame {
+    vvc355_inter_frame pic;       /* the picture (see above) */
+    uint64_t cus;                 /* DEVICE vvc355_affine_cu[n_cus] */
+    uint64_t jobs_luma;           /* DEVICE scratch, vvc355_affine_job[n_jobs] */
+    uint64_t jobs_chroma;         /* DEVICE scratch, vvc355_bipred_job[2 * (n_jobs >> (hs + vs))], Cb and Cr interleaved; unused for 4:0:0 */
+    int32_t  n_cus, n_jobs;       /* n_jobs = the sub-blocks of all records */
+} vvc355_affine_frame;
+/* job arrays only */
+void vvc355_affine_frame_build(void *stream, const vvc355_affine_frame *frame_dev, const vvc355_affine_frame *frame_host);
+/* build, then vvc355_affine_batch on jobs_luma and vvc355_bipred_chroma_batch on jobs_chroma */
+void vvc355_affine_frame_pass(void *stream, int bd, const vvc355_affine_frame *frame_dev, const vvc355_affine_frame *frame_host);
+
+typedef struct vvc355_gpm_cu {
+    int16_t  x0, y0, cb_width, cb_height;     /* luma samples; 8 .. 64 per side, neither side 8 or more times the other */
+    uint8_t  partition_idx;                   /* pu->gpm_partition_idx, 0 .. 63 */
+    uint8_t  slice;                           /* index into frame.slices[] */
+    uint8_t  pad_[2];
+    uint32_t first_job;                       /* running sum of the units' tiles: ceil(w / 16) * ceil(h / 16) per present component */
+    int32_t  gpm_mv[2][6];                    /* pu->gpm_mv[0..1]: two vvc355_mvfield (24 bytes each; declared below) */
+} vvc355_gpm_cu;
+typedef struct vvc355_gpm_frame {
+    vvc355_inter_frame pic;       /* the picture (see above) */
+    uint64_t cus;                 /* DEVICE vvc355_gpm_cu[n_cus] */
+    uint64_t jobs;                /* DEVICE scratch, vvc355_gpm_job[n_jobs]: per unit its luma tiles, then its Cb tiles, then its Cr tiles */
+    int32_t  n_cus, n_jobs;
+} vvc355_gpm_frame;
+/* job arrays only */
+void vvc355_gpm_frame_build(void *stream, const vvc355_gpm_frame *frame_dev, const vvc355_gpm_frame *frame_host);
+/* build, then vvc355_gpm_batch */
+void vvc355_gpm_frame_pass(void *stream, int bd, const vvc355_gpm_frame *frame_dev, const vvc355_gpm_frame *frame_host);
+/* HOST only (no HIP call): the (cb_width >> hs) x (cb_height >> vs) weights, 0 .. 8, row-major into out, that the jobs the GPM
+ * builder writes read for a component of a coding unit of this partition and size: the same masks and the same addressing */
+void vvc355_gpm_weights(int partition_idx, int cb_width, int cb_height, int hs, int vs, uint8_t *out);
 
 /* ------------------------------------------------------------------ affine sub-blocks with PROF (affine.hip) */
 
