@@ -16,6 +16,7 @@ _C = {
     "p": ctypes.c_void_p,
     "q": ctypes.c_ssize_t,     # ptrdiff_t / intptr_t
     "z": ctypes.c_size_t,
+    "u": ctypes.c_uint32,
     "v": None,
 }
 
@@ -146,6 +147,11 @@ BATCH_SIGNATURES = {
     "recon_order":      ("i", "piip"),
     "tab_fill_pass":    ("v", "ppp"),
     "itx_frame_build":  ("v", "ppp"),
+    # packed coefficient levels (vvc355_tb_levels): the transform entries that read them, the int32 adapter, and the host C packer
+    "itx_shape_batch_lv": ("v", "pipppiii"),
+    "itx_batch_lv":     ("v", "pipppii"),
+    "levels_expand":    ("v", "ppppi"),
+    "levels_pack":      ("i", "piippu"),
 }
 
 
@@ -532,6 +538,15 @@ class ItxTu(ctypes.Structure):
     _fields_ = [("coeff_off", ctypes.c_uint32), ("x0", ctypes.c_int16), ("y0", ctypes.c_int16),
                 ("log2_w", ctypes.c_uint8), ("log2_h", ctypes.c_uint8), ("nzw", ctypes.c_uint8), ("nzh", ctypes.c_uint8),
                 ("c_idx", ctypes.c_uint8), ("qp", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("tr", ctypes.c_uint8)]
+
+
+LEVELS_INT32 = 1                     # vvc355_tb_levels.flags bit 0: the block's levels are int32 at job.coeffs
+LEVELS_E_RANGE, LEVELS_E_ZERO_OUT = -1, -2
+
+
+class TbLevels(ctypes.Structure):
+    """Mirror of vvc355_tb_levels (the side record of a block's packed levels)."""
+    _fields_ = [("groups", ctypes.c_uint64), ("first", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 class ItxFrame(ctypes.Structure):

@@ -167,7 +167,52 @@ __device__ __forceinline__ Dequant itx_job_dequant(const vvc355_itx_job &job, in
     return dq;
 }
 
-#define ITX_SYNC()                                                                  \
+// Level source of the _lv entries (vvc355_tb_levels): side records paired with the jobs, and the picture's int16 group stream.
+struct LvSrc {
+    const vvc355_tb_levels *lv;
+    const int16_t *levels;
+};
+// The kernels take it as an optional trailing argument (a pack of zero or one LvSrc), so that their int32 instantiations keep the
+// argument list and the code they had before packed levels existed.
+__device__ __forceinline__ LvSrc lv_src() { return LvSrc{ nullptr, nullptr }; }
+__device__ __forceinline__ LvSrc lv_src(LvSrc s) { return s; }
+// the group of a packed block that holds sample (x, y): first + the number of coded tiles before it in bit order; nullptr when the tile is
+// not coded (or lies beyond the 32 x 32 grid, where nothing is)
+__device__ __forceinline__ const int16_t *lv_group(const vvc355_tb_levels &r, const int16_t *levels, int log2_w, int x, int y)
+{
+    if (x >= 32 || y >= 32)
+        return nullptr;
+    const int b = (y >> 2) * (((1 << min(log2_w, 5)) + 3) >> 2) + (x >> 2);
+    if (!((r.groups >> b) & 1))
+        return nullptr;
+    return levels + ((size_t)r.first + __popcll(r.groups & ((1ull << b) - 1))) * 16;
+}
+__device__ __forceinline__ int lv_level(const vvc355_tb_levels &r, const int16_t *levels, int log2_w, int x, int y)
+{
+    const int16_t *g = lv_group(r, levels, log2_w, x, y);
+    return g ? (int)gld<int16_t>(g + (y & 3) * 4 + (x & 3)) : 0;
+}
+__device__ __forceinline__ int4 unpack_i16x4(uint2 u)
+{
+    return make_int4((int)(int16_t)(u.x & 0xffff), (int)u.x >> 16, (int)(int16_t)(u.y & 0xffff), (int)u.y >> 16);
+}
+// levels e .. e + 3 of a row-major block: 8 bytes of one group when the block is at least 4 wide, single levels otherwise
+__device__ __forceinline__ int4 lv_load4(const vvc355_tb_levels &r, const int16_t *levels, int log2_w, int e)
+{
+    const int w = 1 << log2_w;
+    if (w >= 4) {
+        const int x = e & (w - 1), y = e >> log2_w;
+        const int16_t *g = lv_group(r, levels, log2_w, x, y);
+        return g ? unpack_i16x4(gld<uint2>(g + (y & 3) * 4)) : make_int4(0, 0, 0, 0);
+    }
+    int v[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+        v[q] = lv_level(r, levels, log2_w, (e + q) & (w - 1), (e + q) >> log2_w);
+    return make_int4(v[0], v[1], v[2], v[3]);
+}
+
+#define ITX_SYNC()                                                                \
     do {                                                                            \
         if (WAVE) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } \
         else __syncthreads();                                                       \
@@ -175,8 +220,10 @@ __device__ __forceinline__ Dequant itx_job_dequant(const vvc355_itx_job &job, in
 
 // One transform block of any shape with w * h <= CAP, worked on by the NT lanes `tid` = 0..NT-1 of a group (NT <= 64: the
 // group sits inside one wave and synchronises at wave level; NT = 256: the whole workgroup).  buf / tmp: CAP ints of LDS each.
-template <int BD, int NT, int CAP>
-__device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int *buf, int *tmp, const int8_t *cos_lds, int tid)
+// PACKED: the levels come from the side record `lvr` (groups in `levels`, or int32 at job.coeffs for VVC355_LEVELS_INT32).
+template <int BD, int NT, int CAP, bool PACKED = false>
+__device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int *buf, int *tmp, const int8_t *cos_lds, int tid,
+                                                  const vvc355_tb_levels *lvr = nullptr, const int16_t *levels = nullptr)
 {
     constexpr bool WAVE = NT <= 64;                  // the group lives inside one wave
     const int w = 1 << job.log2_w, h = 1 << job.log2_h, n = w * h;
@@ -207,17 +254,20 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
         }
     }
     const Dequant dq = itx_job_dequant(job, bd);
+    const bool packed = PACKED && !(lvr->flags & VVC355_LEVELS_INT32);
     if (PER < 4) {
 #pragma unroll
         for (int q = 0; q < PER; q++)
-            if (e0 + q < n)
-                buf[e0 + q] = dq.apply(gld<int>(coeffs + e0 + q), (e0 + q) & (w - 1), (e0 + q) >> job.log2_w);
+            if (e0 + q < n) {
+                const int x = (e0 + q) & (w - 1), y = (e0 + q) >> job.log2_w;
+                buf[e0 + q] = dq.apply(packed ? lv_level(*lvr, levels, job.log2_w, x, y) : gld<int>(coeffs + e0 + q), x, y);
+            }
     } else {
 #pragma unroll
         for (int c4 = 0; c4 < PER / 4; c4++) {
             const int e = e0 + c4 * 4;
             if (e < n) {                             // n is a multiple of 4 for every block of >= 4 coefficients
-                int4 v = gld<int4>(coeffs + e);
+                int4 v = packed ? lv_load4(*lvr, levels, job.log2_w, e) : gld<int4>(coeffs + e);
                 if (dq.on) {
                     const int y = e >> job.log2_w, x = e & (w - 1);      // w >= 4 here: the four share a row
                     v.x = dq.apply(v.x, x, y); v.y = dq.apply(v.y, x + 1, y); v.z = dq.apply(v.z, x + 2, y); v.w = dq.apply(v.w, x + 3, y);
@@ -388,9 +438,10 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
 // NT lanes share one block of at most CAP coefficients (CAP / NT = 4 elements per lane, 16 for 64x64):
 //   NT 4 / CAP 16 (4x4), NT 16 / CAP 64 (8x8), NT 64 / CAP 256 (16x16): sub-wave groups, wave-level synchronisation only;
 //   NT 256 / CAP 1024 (32x32) and NT 256 / CAP 4096 (64x64): one workgroup per block.
-template <int BD, int NT, int CAP>
-__global__ __launch_bounds__(256) void itx_kernel(const vvc355_itx_job *__restrict__ jobs, int n_jobs)
+template <int BD, int NT, int CAP, typename... Lv>
+__global__ __launch_bounds__(256) void itx_kernel(const vvc355_itx_job *__restrict__ jobs, int n_jobs, Lv... lv)
 {
+    constexpr bool PACKED = sizeof...(Lv) > 0;       // levels from an LvSrc instead of int32 at job.coeffs
     constexpr int TBS = 256 / NT;                    // blocks per workgroup
     __shared__ __attribute__((aligned(16))) int buf_all[TBS][CAP];
     __shared__ __attribute__((aligned(16))) int tmp_all[TBS][CAP];
@@ -405,7 +456,13 @@ __global__ __launch_bounds__(256) void itx_kernel(const vvc355_itx_job *__restri
     resolve_type(job);
     if (job.log2_w + job.log2_h > __builtin_ctz(CAP))
         return;                                      // larger than this launch's size class: contract violation, skipped
-    itx_generic_block<BD, NT, CAP>(job, buf_all[sub], tmp_all[sub], cos_lds, tid);
+    if constexpr (PACKED) {
+        const LvSrc ls = lv_src(lv...);
+        const vvc355_tb_levels r = ls.lv[ji];
+        itx_generic_block<BD, NT, CAP, true>(job, buf_all[sub], tmp_all[sub], cos_lds, tid, &r, ls.levels);
+    } else {
+        itx_generic_block<BD, NT, CAP>(job, buf_all[sub], tmp_all[sub], cos_lds, tid);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ shape-specialised path
@@ -460,9 +517,12 @@ template <int KS> __device__ __forceinline__ void lds_row(const int16_t *p, uint
     }
 }
 
-template <int BD, int LW, int LH>
-__global__ __launch_bounds__(256) void itx_shape_kernel(const vvc355_itx_job *__restrict__ jobs, int n_jobs)
+// PACKED: a lane whose tile is coded loads its group (32 bytes, two 16-byte loads; its position is a popcount of the lower mask bits),
+// any other lane loads nothing; jobs with VVC355_LEVELS_INT32 read int32 levels as the plain kernel does.
+template <int BD, int LW, int LH, typename... Lv>
+__global__ __launch_bounds__(256) void itx_shape_kernel(const vvc355_itx_job *__restrict__ jobs, int n_jobs, Lv... lv)
 {
+    constexpr bool PACKED = sizeof...(Lv) > 0;
     using px_t = typename Px<BD>::type;
     constexpr int W = 1 << LW, H = 1 << LH, CAP = W * H;
     constexpr int NT = CAP / 16, TBS = 256 / NT;             // lanes per block (one per 4x4 tile), blocks per workgroup
@@ -521,11 +581,28 @@ __global__ __launch_bounds__(256) void itx_shape_kernel(const vvc355_itx_job *__
     const Dequant dq = itx_job_dequant(job, bd);
     const bool need = act && y0 < cntv && x0 < nzw && x0 < KVH;
     unsigned mag = 0;
+    bool packed = false;
+    uint4 pk[2];
+    if constexpr (PACKED) {
+        const LvSrc ls = lv_src(lv...);
+        const vvc355_tb_levels lvr = ls.lv[valid ? ji : n_jobs - 1];
+        packed = !(lvr.flags & VVC355_LEVELS_INT32);
+        const int16_t *g = packed && need ? lv_group(lvr, ls.levels, LW, x0, y0) : nullptr;
+        pk[0] = pk[1] = make_uint4(0, 0, 0, 0);
+        if (g) {
+            pk[0] = gld<uint4>(g);
+            pk[1] = gld<uint4>(g + 8);
+        }
+    }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         int4 v = make_int4(0, 0, 0, 0);
-        if (need && y0 + r < cntv)
+        if (PACKED && packed) {
+            if (y0 + r < cntv)
+                v = unpack_i16x4(r & 1 ? make_uint2(pk[r >> 1].z, pk[r >> 1].w) : make_uint2(pk[r >> 1].x, pk[r >> 1].y));
+        } else if (need && y0 + r < cntv) {
             v = gld<int4>(coeffs + (y0 + r) * W + x0);
+        }
         if (dq.on) {
             const unsigned lv = (unsigned)(v.x ^ (v.x >> 31)) | (unsigned)(v.y ^ (v.y >> 31)) | (unsigned)(v.z ^ (v.z >> 31)) | (unsigned)(v.w ^ (v.w >> 31));
             if ((lv >> 15) == 0) {
@@ -552,8 +629,14 @@ __global__ __launch_bounds__(256) void itx_shape_kernel(const vvc355_itx_job *__
                 break;
             vvc355_itx_job jg = jobs[jb];
             resolve_type(jg);
-            if (jg.log2_w + jg.log2_h <= LW + LH)
-                itx_generic_block<BD, 256, CAP>(jg, gbuf, gtmp, cos_lds, threadIdx.x);
+            if (jg.log2_w + jg.log2_h <= LW + LH) {
+                if constexpr (PACKED) {
+                    const LvSrc ls = lv_src(lv...);
+                    const vvc355_tb_levels r = ls.lv[jb];
+                    itx_generic_block<BD, 256, CAP, true>(jg, gbuf, gtmp, cos_lds, threadIdx.x, &r, ls.levels);
+                } else
+                    itx_generic_block<BD, 256, CAP>(jg, gbuf, gtmp, cos_lds, threadIdx.x);
+            }
             __syncthreads();
         }
         return;
@@ -656,6 +739,33 @@ __global__ __launch_bounds__(256) void itx_shape_kernel(const vvc355_itx_job *__
     }
 }
 #undef ITX_SYNC
+
+// vvc355_levels_expand: one wave per job, lanes over the 4-sample row segments of the job's nzw x nzh window.  A segment is 8 bytes of one
+// group (slots outside a block narrower than 4 are zero in the stream, and no store reaches past nzw <= w).
+__global__ __launch_bounds__(256) void levels_expand_kernel(const vvc355_itx_job *__restrict__ jobs, LvSrc ls, int n_jobs)
+{
+    const int ji = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (ji >= n_jobs)
+        return;
+    const vvc355_tb_levels r = ls.lv[ji];
+    if (r.flags & VVC355_LEVELS_INT32)
+        return;
+    const vvc355_itx_job job = jobs[ji];
+    int *coeffs = (int *)job.coeffs;
+    const int lw = job.log2_w, w = 1 << lw;
+    const int nzw = min((int)job.nzw, w), nzh = min((int)job.nzh, 1 << job.log2_h);
+    const int sw = (nzw + 3) >> 2;                            // row segments per window row
+    for (int u = lane; u < sw * nzh; u += 64) {
+        const int y = u / sw, x0 = (u - y * sw) * 4;
+        const int16_t *g = lv_group(r, ls.levels, lw, x0, y);
+        const int4 v = g ? unpack_i16x4(gld<uint2>(g + (y & 3) * 4)) : make_int4(0, 0, 0, 0);
+        int *row = coeffs + y * w + x0;
+        gst<int>(row, v.x);
+        if (x0 + 1 < nzw) gst<int>(row + 1, v.y);
+        if (x0 + 2 < nzw) gst<int>(row + 2, v.z);
+        if (x0 + 3 < nzw) gst<int>(row + 3, v.w);
+    }
+}
 
 // Scaling process for transform coefficients (vvc_intra.c:277-417): 16 lanes per transform block (most blocks are small and
 // their non-zero windows smaller still), lanes over the scan rectangle.  levelScale / qp arithmetic per derive_qp (:277) and
@@ -809,13 +919,16 @@ static bool itx_entry_exists(int trh, int trv, int lw, int lh)
     return true;
 }
 
-template <int BD, int LW>
-static void launch_itx_shape(hipStream_t st, const vvc355_itx_job *jobs_dev, int n_jobs, int log2_h)
+template <int BD, int LW, bool PACKED = false>
+static void launch_itx_shape(hipStream_t st, const vvc355_itx_job *jobs_dev, int n_jobs, int log2_h, LvSrc ls = {})
 {
 #define VVC355_ITX_SHAPE(LH)                                                                                          \
     case LH: {                                                                                                        \
         constexpr int TBS = 256 / ((1 << (LW + LH)) / 16);                                                            \
-        hipLaunchKernelGGL((itx_shape_kernel<BD, LW, LH>), dim3((n_jobs + TBS - 1) / TBS), dim3(256), 0, st, jobs_dev, n_jobs); \
+        if constexpr (PACKED)                                                                                         \
+            hipLaunchKernelGGL((itx_shape_kernel<BD, LW, LH, LvSrc>), dim3((n_jobs + TBS - 1) / TBS), dim3(256), 0, st, jobs_dev, n_jobs, ls); \
+        else                                                                                                          \
+            hipLaunchKernelGGL((itx_shape_kernel<BD, LW, LH>), dim3((n_jobs + TBS - 1) / TBS), dim3(256), 0, st, jobs_dev, n_jobs); \
     } break;
     switch (log2_h) {
     VVC355_ITX_SHAPE(2) VVC355_ITX_SHAPE(3) VVC355_ITX_SHAPE(4) VVC355_ITX_SHAPE(5) VVC355_ITX_SHAPE(6)
@@ -824,15 +937,15 @@ static void launch_itx_shape(hipStream_t st, const vvc355_itx_job *jobs_dev, int
 }
 
 
-template <int BD>
-static void launch_itx_shape_any(hipStream_t st, const vvc355_itx_job *jobs_dev, int n_jobs, int log2_w, int log2_h)
+template <int BD, bool PACKED = false>
+static void launch_itx_shape_any(hipStream_t st, const vvc355_itx_job *jobs_dev, int n_jobs, int log2_w, int log2_h, LvSrc ls = {})
 {
     switch (log2_w) {
-    case 2: launch_itx_shape<BD, 2>(st, jobs_dev, n_jobs, log2_h); break;
-    case 3: launch_itx_shape<BD, 3>(st, jobs_dev, n_jobs, log2_h); break;
-    case 4: launch_itx_shape<BD, 4>(st, jobs_dev, n_jobs, log2_h); break;
-    case 5: launch_itx_shape<BD, 5>(st, jobs_dev, n_jobs, log2_h); break;
-    case 6: launch_itx_shape<BD, 6>(st, jobs_dev, n_jobs, log2_h); break;
+    case 2: launch_itx_shape<BD, 2, PACKED>(st, jobs_dev, n_jobs, log2_h, ls); break;
+    case 3: launch_itx_shape<BD, 3, PACKED>(st, jobs_dev, n_jobs, log2_h, ls); break;
+    case 4: launch_itx_shape<BD, 4, PACKED>(st, jobs_dev, n_jobs, log2_h, ls); break;
+    case 5: launch_itx_shape<BD, 5, PACKED>(st, jobs_dev, n_jobs, log2_h, ls); break;
+    case 6: launch_itx_shape<BD, 6, PACKED>(st, jobs_dev, n_jobs, log2_h, ls); break;
     }
 }
 
@@ -918,6 +1031,42 @@ void vvc355_itx_shape_batch(void *stream, int bd, const vvc355_itx_job *jobs_dev
     }
     hipStream_t st = (hipStream_t)stream;
     VVC355_BD_DISPATCH(bd, launch_itx_shape_any<BD>(st, jobs_dev, n_jobs, log2_w, log2_h));
+    HIP_CHECK(hipGetLastError());
+}
+
+void vvc355_itx_batch_lv(void *stream, int bd, const vvc355_itx_job *jobs_dev, const vvc355_tb_levels *lv_dev, const int16_t *levels_dev,
+                         int n_jobs, int max_log2_area)
+{
+    if (n_jobs <= 0) return;
+    hipStream_t st = (hipStream_t)stream;
+    const LvSrc ls = { lv_dev, levels_dev };
+    VVC355_BD_DISPATCH(bd, {
+        if (max_log2_area <= 4)       hipLaunchKernelGGL((itx_kernel<BD, 4, 16, LvSrc>), dim3((n_jobs + 63) / 64), dim3(256), 0, st, jobs_dev, n_jobs, ls);
+        else if (max_log2_area <= 6)  hipLaunchKernelGGL((itx_kernel<BD, 16, 64, LvSrc>), dim3((n_jobs + 15) / 16), dim3(256), 0, st, jobs_dev, n_jobs, ls);
+        else if (max_log2_area <= 8)  hipLaunchKernelGGL((itx_kernel<BD, 64, 256, LvSrc>), dim3((n_jobs + 3) / 4), dim3(256), 0, st, jobs_dev, n_jobs, ls);
+        else if (max_log2_area <= 10) hipLaunchKernelGGL((itx_kernel<BD, 256, 1024, LvSrc>), dim3(n_jobs), dim3(256), 0, st, jobs_dev, n_jobs, ls);
+        else                          hipLaunchKernelGGL((itx_kernel<BD, 256, 4096, LvSrc>), dim3(n_jobs), dim3(256), 0, st, jobs_dev, n_jobs, ls);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
+void vvc355_itx_shape_batch_lv(void *stream, int bd, const vvc355_itx_job *jobs_dev, const vvc355_tb_levels *lv_dev, const int16_t *levels_dev,
+                               int n_jobs, int log2_w, int log2_h)
+{
+    if (n_jobs <= 0) return;
+    if (log2_w < 2 || log2_w > 6 || log2_h < 2 || log2_h > 6) {
+        vvc355_itx_batch_lv(stream, bd, jobs_dev, lv_dev, levels_dev, n_jobs, log2_w + log2_h);
+        return;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    VVC355_BD_DISPATCH(bd, (launch_itx_shape_any<BD, true>(st, jobs_dev, n_jobs, log2_w, log2_h, LvSrc{ lv_dev, levels_dev })));
+    HIP_CHECK(hipGetLastError());
+}
+
+void vvc355_levels_expand(void *stream, const vvc355_itx_job *jobs_dev, const vvc355_tb_levels *lv_dev, const int16_t *levels_dev, int n_jobs)
+{
+    if (n_jobs <= 0) return;
+    hipLaunchKernelGGL(levels_expand_kernel, dim3((n_jobs + 3) / 4), dim3(256), 0, (hipStream_t)stream, jobs_dev, LvSrc{ lv_dev, levels_dev }, n_jobs);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -329,6 +329,44 @@ typedef struct vvc355_itx_frame {
 void vvc355_itx_frame_build(void *stream, const vvc355_itx_frame *frame_dev, const vvc355_itx_frame *frame_host);
 
 /*
+ * Packed coefficient levels: what a parser hands over instead of the int32 arena (4 bytes per sample of every coded block, zeros included).
+ *   level stream  one picture's levels as int16 GROUPS of 16 (32 bytes): one 4x4 tile of a transform block, row-major, slot (y & 3) * 4 + (x & 3);
+ *                 the stream base is 32-byte aligned.  Without extended precision every level fits int16 (CoeffMinY / CoeffMaxY, range 15).
+ *   side record   one vvc355_tb_levels per transform block, indexed like the jobs it goes with: lv[i] belongs to jobs[i] (a caller that launches
+ *                 a sub-range offsets both pointers alike; the jobs vvc355_itx_frame_build writes are in record order).
+ *                 groups: bit gy * gw + gx set = the tile at (4 gx, 4 gy) is in the stream, gw = ceil(min(w, 32) / 4); the grid covers
+ *                 min(w, 32) x min(h, 32) (nothing beyond 32 is coded: zero-out), so at most 8 x 8 bits.  Blocks narrower or lower than 4
+ *                 (2xN, Nx2, 1x16, 16x1) use one partial tile per 4 rows / columns; slots outside the block are zero.
+ *                 first: stream index of the block's first group; its groups follow in increasing bit order.
+ *                 flags bit 0 (VVC355_LEVELS_INT32): not packed, the levels are int32 at job.coeffs as for the plain entries (extended precision).
+ * For a packed job, job.coeffs is only the int32 OUTPUT (store_coeffs): residuals still land in the device arena the in-order intra pass and the
+ * chroma residual stage read, but no levels are read from it.
+ */
+typedef struct vvc355_tb_levels {
+    uint64_t groups;
+    uint32_t first;
+    uint32_t flags;
+} vvc355_tb_levels;
+enum { VVC355_LEVELS_INT32 = 1 };
+/* vvc355_itx_shape_batch / vvc355_itx_batch with the levels taken from lv[i] (packed groups in `levels`, DEVICE int16, or int32 at
+ * jobs[i].coeffs for VVC355_LEVELS_INT32); one launch may mix both kinds. */
+void vvc355_itx_shape_batch_lv(void *stream, int bd, const vvc355_itx_job *jobs_dev, const vvc355_tb_levels *lv_dev, const int16_t *levels_dev,
+    int n_jobs, int log2_w, int log2_h);
+void vvc355_itx_batch_lv(void *stream, int bd, const vvc355_itx_job *jobs_dev, const vvc355_tb_levels *lv_dev, const int16_t *levels_dev,
+    int n_jobs, int max_log2_area);
+/* The adapter for consumers that read int32 levels (vvc355_lfnst_batch, vvc355_dequant_batch with transform skip, BDPCM): writes every packed
+ * job's [0, nzw) x [0, nzh) window into the int32 arena at job.coeffs (row stride w) — coded groups with their levels, the rest of the window
+ * zero — and nothing outside it.  The window must cover what the next consumer reads: w x h for transform-skip and BDPCM blocks, the
+ * window of the transform that follows LFNST (4 or 8) for LFNST blocks.  Jobs with VVC355_LEVELS_INT32 are left alone. */
+void vvc355_levels_expand(void *stream, const vvc355_itx_job *jobs_dev, const vvc355_tb_levels *lv_dev, const int16_t *levels_dev, int n_jobs);
+/* Host C, per transform block right after residual coding (ff_vvc_residual_coding): reads the block's int32 levels (row-major, w x h),
+ * appends its coded groups at `out` and fills *lv (first = `first`).  Returns the number of groups written, or VVC355_LEVELS_E_RANGE for a
+ * level outside int16 / VVC355_LEVELS_E_ZERO_OUT for a non-zero level at x >= 32 or y >= 32: nothing is written to `out` then, *lv is
+ * {0, first, VVC355_LEVELS_INT32} and the block stays on the int32 path. */
+enum { VVC355_LEVELS_E_RANGE = -1, VVC355_LEVELS_E_ZERO_OUT = -2 };
+int  vvc355_levels_pack(const int32_t *coeffs, int log2_w, int log2_h, int16_t *out, vvc355_tb_levels *lv, uint32_t first);
+
+/*
  * Scaling process for transform coefficients (dequant) — NOT a table slot in the reference: host C in
  * vvc_intra.c:277-417 (derive_qp :277, derive_scale :311, derive_scale_m :341, scale_coeff :391, dequant :400),
  * called per transform block right before LFNST / itx (vvc_intra.c:455-462).  Flattened: everything read through
