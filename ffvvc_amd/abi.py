@@ -152,6 +152,8 @@ BATCH_SIGNATURES = {
     "itx_batch_lv":     ("v", "pipppii"),
     "levels_expand":    ("v", "ppppi"),
     "levels_pack":      ("i", "piippu"),
+    # the intra transform stage from 16-byte records (vvc355_intra_tu): scaling + LFNST + transform in one kernel, no job array
+    "intra_tb_pass":    ("i", "ppp"),
 }
 
 
@@ -547,6 +549,25 @@ LEVELS_E_RANGE, LEVELS_E_ZERO_OUT = -1, -2
 class TbLevels(ctypes.Structure):
     """Mirror of vvc355_tb_levels (the side record of a block's packed levels)."""
     _fields_ = [("groups", ctypes.c_uint64), ("first", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class IntraTu(ctypes.Structure):
+    """Mirror of vvc355_intra_tu (one transform block of an intra coding unit)."""
+    _fields_ = [("coeff_off", ctypes.c_uint32),
+                ("log2_w", ctypes.c_uint8), ("log2_h", ctypes.c_uint8), ("nzw", ctypes.c_uint8), ("nzh", ctypes.c_uint8),
+                ("c_idx", ctypes.c_uint8), ("qp", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("tu_flags", ctypes.c_uint8),
+                ("mts_idx", ctypes.c_uint8), ("lfnst_idx", ctypes.c_uint8), ("pred_mode_intra", ctypes.c_int8), ("pad_", ctypes.c_uint8)]
+
+
+INTRA_TU_DEP_QUANT, INTRA_TU_LFNST = 1, 2
+INTRA_TB_E_CLASS, INTRA_TB_E_BD, INTRA_TB_E_RANGE, INTRA_TB_E_LEVELS, INTRA_TB_E_MODE = -1, -2, -3, -4, -5
+
+
+class IntraTbFrame(ctypes.Structure):
+    """Mirror of vvc355_intra_tb_frame."""
+    _fields_ = [("tus", ctypes.c_uint64), ("coeffs", ctypes.c_uint64), ("lv", ctypes.c_uint64), ("levels", ctypes.c_uint64),
+                ("n_tus", ctypes.c_int32), ("class_first", ctypes.c_int32 * 6),
+                ("range", ctypes.c_uint8), ("bd", ctypes.c_uint8), ("launch_mode", ctypes.c_uint8), ("pad_", ctypes.c_uint8)]
 
 
 class ItxFrame(ctypes.Structure):

@@ -221,13 +221,17 @@ __device__ __forceinline__ int4 lv_load4(const vvc355_tb_levels &r, const int16_
 // One transform block of any shape with w * h <= CAP, worked on by the NT lanes `tid` = 0..NT-1 of a group (NT <= 64: the
 // group sits inside one wave and synchronises at wave level; NT = 256: the whole workgroup).  buf / tmp: CAP ints of LDS each.
 // PACKED: the levels come from the side record `lvr` (groups in `levels`, or int32 at job.coeffs for VVC355_LEVELS_INT32).
-template <int BD, int NT, int CAP, bool PACKED = false>
+// LFNST: with lf_idx = 1 / 2 the staged block goes through ilfnst_transform (vvc_intra.c:65-127) between the scaling process and the column
+// pass (the intra record path; lf_idx, lf_mode are uniform over the group, w and h are at least 4).
+template <int BD, int NT, int CAP, bool PACKED = false, bool LFNST = false>
 __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int *buf, int *tmp, const int8_t *cos_lds, int tid,
-                                                  const vvc355_tb_levels *lvr = nullptr, const int16_t *levels = nullptr)
+                                                  const vvc355_tb_levels *lvr = nullptr, const int16_t *levels = nullptr,
+                                                  int lf_idx = 0, int lf_mode = 0)
 {
     constexpr bool WAVE = NT <= 64;                  // the group lives inside one wave
     const int w = 1 << job.log2_w, h = 1 << job.log2_h, n = w * h;
-    const int nzw = job.nzw, nzh = job.nzh, range = job.range, bd = job.bd ? job.bd : BD;
+    int nzw = job.nzw, nzh = job.nzh;
+    const int range = job.range, bd = job.bd ? job.bd : BD;
     int *coeffs = (int *)job.coeffs;
 
     // I/O mapping: lane `tid` owns the PER consecutive elements starting at tid * PER (row-major), so coefficients move as
@@ -277,6 +281,54 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
         }
     }
     ITX_SYNC();
+
+    if constexpr (LFNST) {
+        if (lf_idx) {
+            // The first 8 / 16 scaled levels in 4x4 diagonal scan order times the 16x16 / 16x48 matrix of (set, lf_idx), rounded and clipped
+            // (ff_vvc_inv_lfnst_1d, vvc_itx_1d.c:708), into the top-left 4x4 or the 8x8 L-shape, transposed for modes above 34: the
+            // arithmetic of lfnst_batch_kernel, with the outputs spread over the group's lanes.  The L-shape overlaps the scan positions,
+            // so nothing is written before every lane has finished reading.
+            constexpr int MAXO = NT >= 64 ? 1 : NT == 16 ? 3 : 4;        // outputs per lane: ceil(48 / NT); 4 lanes only ever hold a 4x4
+            const bool big = w >= 8 && h >= 8;
+            const int n_out = big ? 48 : 16;
+            const int nz = ((w == 8 && h == 8) || (w == 4 && h == 4)) ? 8 : 16;
+            const int set = lf_mode < 0 ? 1 : d_tab_lfnst_tr_set_index[lf_mode];
+            const int8_t *m = big ? d_tab_lfnst_8x8 + (set * 2 + lf_idx - 1) * 16 * 48 : d_tab_lfnst_4x4 + (set * 2 + lf_idx - 1) * 16 * 16;
+            unsigned t[MAXO];
+#pragma unroll
+            for (int q = 0; q < MAXO; q++)
+                t[q] = 0;
+            for (int i = 0; i < nz; i++) {
+                const unsigned u = (unsigned)buf[w * (int)((kDiag4Y >> (4 * i)) & 15) + (int)((kDiag4X >> (4 * i)) & 15)];
+#pragma unroll
+                for (int q = 0; q < MAXO; q++) {
+                    const int j = tid + q * NT;
+                    if (j < n_out)
+                        t[q] += u * (unsigned)(int)m[i * n_out + j];
+                }
+            }
+            ITX_SYNC();
+#pragma unroll
+            for (int q = 0; q < MAXO; q++) {
+                const int j = tid + q * NT;
+                if (j < n_out) {
+                    int x, y;
+                    if (lf_mode > 34) {         // transposed placement (:86-110)
+                        if (!big)        { y = j & 3; x = j >> 2; }
+                        else if (j < 32) { y = j & 7; x = j >> 3; }
+                        else             { y = (j - 32) & 3; x = 4 + ((j - 32) >> 2); }
+                    } else {                    // row by row: 8 (4) values in rows 0..3, 4 in rows 4..7 (:111-120)
+                        if (!big)        { y = j >> 2; x = j & 3; }
+                        else if (j < 32) { y = j >> 3; x = j & 7; }
+                        else             { y = 4 + ((j - 32) >> 2); x = (j - 32) & 3; }
+                    }
+                    buf[y * w + x] = clip_intp2(((int)t[q] + 64) >> 7, range);
+                }
+            }
+            nzw = nzh = big ? 8 : 4;
+            ITX_SYNC();
+        }
+    }
 
     const bool dc_only = job.trh == TX_DCT2 && job.trv == TX_DCT2 && nzw == 1 && nzh == 1;
     int sh_final;
@@ -994,6 +1046,118 @@ __global__ __launch_bounds__(256) void itx_build_kernel(const vvc355_itx_frame *
     }
 }
 
+// ------------------------------------------------------------------------------------------------ intra transform stage from records
+//
+// vvc355_intra_tb_pass: a group of NT lanes turns one 16-byte vvc355_intra_tu into the job itx_generic_block consumes, in registers (what
+// itx_build_kernel writes to memory for the inter path), and runs scaling + LFNST + transform on it.  The residual stays in the arena
+// (dst = 0), so the pixel type of the add path plays no part and the kernels are not specialised by bit depth: the block template is
+// entered with BD = 10 and job.bd = the frame's.
+// Records [first, end) of one area class, `wg` = workgroup index inside the class; buf / tmp: 256 / NT blocks of CAP ints each.
+template <int NT, int CAP, bool PACKED>
+__device__ __forceinline__ void intra_tb_group(const vvc355_intra_tb_frame &f, int first, int end, int wg, int *buf, int *tmp,
+                                               const int8_t *cos_lds)
+{
+    constexpr int TBS = 256 / NT;                    // blocks per workgroup
+    const int sub = threadIdx.x / NT, tid = threadIdx.x % NT;
+    const int i = first + wg * TBS + sub;
+    if (i >= end)
+        return;                                      // whole groups leave together
+    const vvc355_intra_tu t = ((const vvc355_intra_tu *)f.tus)[i];
+    const int lw = t.log2_w, lh = t.log2_h;
+    const bool lfnst = t.flags & VVC355_INTRA_TU_LFNST;
+    // contract violations are skipped, never executed: the area bounds the LDS tile and the arena slot, 4 coefficients are the unit of the
+    // vector loads, 64 the largest transform, and LFNST reads a 4x4 corner and a table row picked by lfnst_idx / pred_mode_intra
+    if (lw + lh > __builtin_ctz(CAP) || lw + lh < 2 || lw > 6 || lh > 6 || (t.flags & ~(VVC355_INTRA_TU_DEP_QUANT | VVC355_INTRA_TU_LFNST)))
+        return;
+    if (lfnst && (lw < 2 || lh < 2 || t.lfnst_idx < 1 || t.lfnst_idx > 2 || t.pred_mode_intra > 94))
+        return;
+    vvc355_itx_job job = {};
+    job.coeffs = f.coeffs + (uint64_t)t.coeff_off * 4;
+    job.log2_w = t.log2_w; job.log2_h = t.log2_h;
+    job.nzw = (uint8_t)min((int)t.nzw, 1 << lw); job.nzh = (uint8_t)min((int)t.nzh, 1 << lh);
+    job.range = f.range; job.bd = f.bd;
+    job.store_coeffs = 1;
+    job.dq_flags = (uint8_t)(1 | ((t.flags & VVC355_INTRA_TU_DEP_QUANT) << 1)); job.dq_qp = t.qp;
+    job.log2_matrix_size = 1; job.dc = -1;
+    job.mts_flags = VVC355_ITX_DERIVE_TYPE; job.tu_flags = t.tu_flags; job.mts_idx = t.mts_idx; job.lfnst_idx = t.lfnst_idx; job.c_idx = t.c_idx;
+    resolve_type(job);
+    if constexpr (PACKED) {
+        const vvc355_tb_levels r = ((const vvc355_tb_levels *)f.lv)[i];
+        itx_generic_block<10, NT, CAP, true, true>(job, buf + sub * CAP, tmp + sub * CAP, cos_lds, tid, &r, (const int16_t *)f.levels,
+                                                   lfnst ? t.lfnst_idx : 0, t.pred_mode_intra);
+    } else {
+        itx_generic_block<10, NT, CAP, false, true>(job, buf + sub * CAP, tmp + sub * CAP, cos_lds, tid, nullptr, nullptr,
+                                                    lfnst ? t.lfnst_idx : 0, t.pred_mode_intra);
+    }
+}
+
+// one area class per launch (launch_mode 1, and the 64x64 class of either mode)
+template <int NT, int CAP, bool PACKED>
+__global__ __launch_bounds__(256) void intra_tb_kernel(const vvc355_intra_tb_frame *__restrict__ fp, int first, int end)
+{
+    constexpr int TBS = 256 / NT;
+    __shared__ __attribute__((aligned(16))) int buf_all[TBS * CAP];
+    __shared__ __attribute__((aligned(16))) int tmp_all[TBS * CAP];
+    __shared__ int8_t cos_lds[256];
+    cos_lds[threadIdx.x] = d_tab_dct2_cos[threadIdx.x];
+    __syncthreads();
+    const vvc355_intra_tb_frame f = load_uniform(fp);
+    intra_tb_group<NT, CAP, PACKED>(f, first, end, blockIdx.x, buf_all, tmp_all, cos_lds);
+}
+
+// classes 0..3 in one grid (launch_mode 2): class 0 owns the workgroups below wg_first[0], class k those in [wg_first[k - 1], wg_first[k]);
+// the host computes the four offsets from the class counts.  Every class fills the same 2 x 1024 ints of LDS, with 64 / 16 / 4 / 1 blocks
+struct IntraTbGrid {
+    int wg_first[4];                                 // first workgroup of classes 1, 2, 3 and the end of class 3 (= the grid)
+};
+template <bool PACKED>
+__global__ __launch_bounds__(256) void intra_tb_merged_kernel(const vvc355_intra_tb_frame *__restrict__ fp, IntraTbGrid g)
+{
+    __shared__ __attribute__((aligned(16))) int buf_all[1024];
+    __shared__ __attribute__((aligned(16))) int tmp_all[1024];
+    __shared__ int8_t cos_lds[256];
+    cos_lds[threadIdx.x] = d_tab_dct2_cos[threadIdx.x];
+    __syncthreads();
+    const vvc355_intra_tb_frame f = load_uniform(fp);
+    const int b = blockIdx.x;
+    if (b < g.wg_first[0])
+        intra_tb_group<4, 16, PACKED>(f, f.class_first[0], f.class_first[1], b, buf_all, tmp_all, cos_lds);
+    else if (b < g.wg_first[1])
+        intra_tb_group<16, 64, PACKED>(f, f.class_first[1], f.class_first[2], b - g.wg_first[0], buf_all, tmp_all, cos_lds);
+    else if (b < g.wg_first[2])
+        intra_tb_group<64, 256, PACKED>(f, f.class_first[2], f.class_first[3], b - g.wg_first[1], buf_all, tmp_all, cos_lds);
+    else if (b < g.wg_first[3])
+        intra_tb_group<256, 1024, PACKED>(f, f.class_first[3], f.class_first[4], b - g.wg_first[2], buf_all, tmp_all, cos_lds);
+}
+
+// which launch shape launch_mode 0 takes: the faster one on the bench's 8K picture (tools/intra_tb_time.py measures both)
+static constexpr int kIntraTbDefaultMode = 2;
+
+template <bool PACKED>
+static void launch_intra_tb(hipStream_t st, const vvc355_intra_tb_frame *fd, const vvc355_intra_tb_frame &fh, int mode)
+{
+    const int32_t *cf = fh.class_first;
+    int wgs[5];
+    for (int k = 0; k < 5; k++) {
+        const int cnt = cf[k + 1] - cf[k], tbs = k == 0 ? 64 : k == 1 ? 16 : k == 2 ? 4 : 1;
+        wgs[k] = (cnt + tbs - 1) / tbs;
+    }
+    if (mode == 2) {
+        IntraTbGrid g;
+        int total = 0;
+        for (int k = 0; k < 4; k++)
+            g.wg_first[k] = total += wgs[k];
+        if (total)
+            hipLaunchKernelGGL((intra_tb_merged_kernel<PACKED>), dim3(total), dim3(256), 0, st, fd, g);
+    } else {
+        if (wgs[0]) hipLaunchKernelGGL((intra_tb_kernel<4, 16, PACKED>), dim3(wgs[0]), dim3(256), 0, st, fd, cf[0], cf[1]);
+        if (wgs[1]) hipLaunchKernelGGL((intra_tb_kernel<16, 64, PACKED>), dim3(wgs[1]), dim3(256), 0, st, fd, cf[1], cf[2]);
+        if (wgs[2]) hipLaunchKernelGGL((intra_tb_kernel<64, 256, PACKED>), dim3(wgs[2]), dim3(256), 0, st, fd, cf[2], cf[3]);
+        if (wgs[3]) hipLaunchKernelGGL((intra_tb_kernel<256, 1024, PACKED>), dim3(wgs[3]), dim3(256), 0, st, fd, cf[3], cf[4]);
+    }
+    if (wgs[4]) hipLaunchKernelGGL((intra_tb_kernel<256, 4096, PACKED>), dim3(wgs[4]), dim3(256), 0, st, fd, cf[4], cf[5]);
+}
+
 } // namespace vvc355
 
 using namespace vvc355;
@@ -1020,6 +1184,33 @@ void vvc355_itx_frame_build(void *stream, const vvc355_itx_frame *frame_dev, con
     if (frame_host->n_tus <= 0) return;
     hipLaunchKernelGGL(vvc355::itx_build_kernel, dim3((frame_host->n_tus + 255) / 256), dim3(256), 0, (hipStream_t)stream, frame_dev);
     HIP_CHECK(hipGetLastError());
+}
+
+int vvc355_intra_tb_pass(void *stream, const vvc355_intra_tb_frame *frame_dev, const vvc355_intra_tb_frame *frame_host)
+{
+    // the host copy is checked before any HIP call: a refused frame launches nothing
+    if (!frame_host || frame_host->n_tus < 0 || frame_host->class_first[0] != 0 || frame_host->class_first[5] != frame_host->n_tus)
+        return VVC355_INTRA_TB_E_CLASS;
+    for (int k = 0; k < 5; k++)
+        if (frame_host->class_first[k] > frame_host->class_first[k + 1])
+            return VVC355_INTRA_TB_E_CLASS;
+    if (frame_host->bd != 8 && frame_host->bd != 10 && frame_host->bd != 12)
+        return VVC355_INTRA_TB_E_BD;
+    if (frame_host->range < 15 || frame_host->range > 20)
+        return VVC355_INTRA_TB_E_RANGE;
+    if (!frame_host->lv != !frame_host->levels)
+        return VVC355_INTRA_TB_E_LEVELS;
+    if (frame_host->launch_mode > 2)
+        return VVC355_INTRA_TB_E_MODE;
+    if (frame_host->n_tus == 0)
+        return 0;
+    const int mode = frame_host->launch_mode ? frame_host->launch_mode : kIntraTbDefaultMode;
+    if (frame_host->lv)
+        launch_intra_tb<true>((hipStream_t)stream, frame_dev, *frame_host, mode);
+    else
+        launch_intra_tb<false>((hipStream_t)stream, frame_dev, *frame_host, mode);
+    HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 void vvc355_itx_shape_batch(void *stream, int bd, const vvc355_itx_job *jobs_dev, int n_jobs, int log2_w, int log2_h)

@@ -367,6 +367,57 @@ enum { VVC355_LEVELS_E_RANGE = -1, VVC355_LEVELS_E_ZERO_OUT = -2 };
 int  vvc355_levels_pack(const int32_t *coeffs, int log2_w, int log2_h, int16_t *out, vvc355_tb_levels *lv, uint32_t first);
 
 /*
+ * The transform stage of a picture's INTRA coding units from one 16-byte record per transform block: itransform (vvc_intra.c:432-466) as
+ * dequant -> ilfnst_transform (:65-127) -> derive_transform_type (:130-164) -> itx, in one kernel per block.  No job array is built or
+ * uploaded and no job-build launch precedes it: the kernel makes its vvc355_itx_job in registers (flat scaling matrix, fused scaling
+ * process, the transform types derived from the record's own tu_flags / mts_idx / lfnst_idx / c_idx), reads the levels from the packed
+ * stream (or int32 in place), does LFNST on the staged block and leaves the residual in the arena slot at coeff_off, where the in-order
+ * RECON pass adds it.  Transform skip, BDPCM, joint Cb-Cr and scaling lists are NOT covered: such blocks stay with vvc355_dequant_batch
+ * and the BDPCM / residual entries.
+ *
+ * Record order: the records are GROUPED BY AREA CLASS (log2_w + log2_h <= 4, 6, 8, 10, 12 -> class 0..4), class_first[k] .. class_first[k + 1]
+ * being class k.  Grouping is the host's job, as shape grouping is for vvc355_itx_frame_build: a parser appends to five lists and
+ * concatenates them at upload.  The order inside a class is free, and so is the order of the arena slots: RECON addresses residuals by
+ * coeff_off.  A block may be filed under a LARGER class than its area needs (slower, still correct).  lv[i] belongs to tus[i].
+ * coeff_off must be a multiple of 4 elements: the kernels move coefficients as 16-byte vectors (a block has at least 4, and the slots of
+ * an arena that packs blocks back to back are aligned by construction: every block size is a multiple of 4).
+ *
+ * A record that breaks the contract — an area larger than its class holds, fewer than 4 coefficients, a dimension beyond 64, reserved
+ * flag bits, the LFNST bit with log2_w < 2, log2_h < 2, lfnst_idx not 1 or 2 or pred_mode_intra above 94 — is SKIPPED: nothing is read or
+ * written for it (the vvc355_itx_batch convention for an oversized job).  nzw / nzh are clamped to the block.
+ */
+typedef struct vvc355_intra_tu {
+    uint32_t coeff_off;        /* the block's w*h int32 slot in the residual arena (elements): OUTPUT; also the levels when not packed */
+    uint8_t  log2_w, log2_h, nzw, nzh;     /* nzw/nzh = max_scan_x/y + 1 as residual coding left them (before LFNST resets them) */
+    uint8_t  c_idx, qp, flags, tu_flags;   /* flags bit 0 = sh_dep_quant_used_flag, bit 1 = cu->apply_lfnst_flag[c_idx]; other bits reserved, must be 0 */
+                                           /* tu_flags = VVC355_TU_* of THIS block's coding unit (and SPS) */
+    uint8_t  mts_idx, lfnst_idx;
+    int8_t   pred_mode_intra;  /* what derive_ilfnst_pred_mode_intra (:34-62) returns; read only with flags bit 1 */
+    uint8_t  pad_;
+} vvc355_intra_tu;
+enum { VVC355_INTRA_TU_DEP_QUANT = 1, VVC355_INTRA_TU_LFNST = 2 };
+
+typedef struct vvc355_intra_tb_frame {
+    uint64_t tus;              /* DEVICE vvc355_intra_tu[n_tus], grouped by area class, see class_first */
+    uint64_t coeffs;           /* DEVICE int32 residual arena */
+    uint64_t lv, levels;       /* DEVICE vvc355_tb_levels[n_tus] paired by index + the int16 group stream; both 0 = int32 levels in place at coeff_off */
+    int32_t  n_tus;
+    int32_t  class_first[6];   /* records [class_first[k], class_first[k+1]) have log2_w + log2_h in class k: <=4, <=6, <=8, <=10, <=12 */
+    uint8_t  range, bd;
+    uint8_t  launch_mode;      /* 0 = the library's choice (the faster one, as measured); 1 = one launch per class; 2 = classes 0-3 in one grid */
+    uint8_t  pad_;
+} vvc355_intra_tb_frame;
+
+/* what vvc355_intra_tb_pass returns for a frame it refuses: class_first not non-decreasing from 0 to n_tus (or n_tus < 0, or no frame);
+ * bd not 8 / 10 / 12; range outside 15..20; only one of lv / levels set; launch_mode above 2 */
+enum { VVC355_INTRA_TB_E_CLASS = -1, VVC355_INTRA_TB_E_BD = -2, VVC355_INTRA_TB_E_RANGE = -3, VVC355_INTRA_TB_E_LEVELS = -4,
+       VVC355_INTRA_TB_E_MODE = -5 };
+/* Runs the stage on `stream`: at most two launches (classes 0-3 share one grid, the 64x64 class has its own), or one per non-empty class
+ * with launch_mode 1.  The host copy of the frame is checked before any HIP call.
+ * returns 0, or a negative VVC355_INTRA_TB_E_* with NOTHING launched */
+int vvc355_intra_tb_pass(void *stream, const vvc355_intra_tb_frame *frame_dev, const vvc355_intra_tb_frame *frame_host);
+
+/*
  * Scaling process for transform coefficients (dequant) — NOT a table slot in the reference: host C in
  * vvc_intra.c:277-417 (derive_qp :277, derive_scale :311, derive_scale_m :341, scale_coeff :391, dequant :400),
  * called per transform block right before LFNST / itx (vvc_intra.c:455-462).  Flattened: everything read through
