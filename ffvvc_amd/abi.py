@@ -154,6 +154,8 @@ BATCH_SIGNATURES = {
     "levels_pack":      ("i", "piippu"),
     # the intra transform stage from 16-byte records (vvc355_intra_tu): scaling + LFNST + transform in one kernel, no job array
     "intra_tb_pass":    ("i", "ppp"),
+    # the transform stage of the other coding units from 16-byte records (vvc355_inter_tu): transform + (scaled, joint) residual add
+    "inter_tb_pass":    ("i", "pppi"),
 }
 
 
@@ -568,6 +570,29 @@ class IntraTbFrame(ctypes.Structure):
     _fields_ = [("tus", ctypes.c_uint64), ("coeffs", ctypes.c_uint64), ("lv", ctypes.c_uint64), ("levels", ctypes.c_uint64),
                 ("n_tus", ctypes.c_int32), ("class_first", ctypes.c_int32 * 6),
                 ("range", ctypes.c_uint8), ("bd", ctypes.c_uint8), ("launch_mode", ctypes.c_uint8), ("pad_", ctypes.c_uint8)]
+
+
+class InterTu(ctypes.Structure):
+    """Mirror of vvc355_inter_tu (one coded transform block outside the in-order pass)."""
+    _fields_ = [("coeff_off", ctypes.c_uint32), ("x0", ctypes.c_int16), ("y0", ctypes.c_int16),
+                ("log2_w", ctypes.c_uint8), ("log2_h", ctypes.c_uint8), ("nzw", ctypes.c_uint8), ("nzh", ctypes.c_uint8),
+                ("qp", ctypes.c_uint8), ("tu_flags", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("joint_mts", ctypes.c_uint8)]
+
+
+# vvc355_inter_tu.flags: bits 0-1 c_idx, then these; joint_mts = joint (bits 0-3) | mts_idx << 4
+INTER_TU_DEP_QUANT, INTER_TU_KEEP, INTER_TU_UNIT_DX, INTER_TU_UNIT_DY = 4, 8, 16, 32
+INTER_TB_BINS = 26
+(INTER_TB_E_BINS, INTER_TB_E_BD, INTER_TB_E_RANGE, INTER_TB_E_LEVELS, INTER_TB_E_SIZE_Y, INTER_TB_E_SHIFT, INTER_TB_E_CHANNELS,
+ INTER_TB_E_ORDER) = -1, -2, -3, -4, -5, -6, -7, -8
+
+
+class InterTbFrame(ctypes.Structure):
+    """Mirror of vvc355_inter_tb_frame."""
+    _fields_ = [("tus", ctypes.c_uint64), ("coeffs", ctypes.c_uint64), ("lv", ctypes.c_uint64), ("levels", ctypes.c_uint64),
+                ("plane", ctypes.c_uint64 * 3), ("scale_table", ctypes.c_uint64), ("stride", ctypes.c_int32 * 3),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_tus", ctypes.c_int32),
+                ("hs", ctypes.c_uint8), ("vs", ctypes.c_uint8), ("size_y", ctypes.c_uint8), ("range", ctypes.c_uint8), ("bd", ctypes.c_uint8),
+                ("pad_", ctypes.c_uint8 * 3), ("bin_first", (ctypes.c_int32 * (INTER_TB_BINS + 1)) * 2)]
 
 
 class ItxFrame(ctypes.Structure):

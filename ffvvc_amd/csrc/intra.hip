@@ -10,6 +10,7 @@
 #include <type_traits>
 #include "common.hpp"
 #include "runtime.hpp"
+#include "resid_math.hpp"
 #include "../../include/vvc_mi355.h"
 
 namespace vvc355 {
@@ -1226,15 +1227,7 @@ __device__ __forceinline__ int lmcs_scale_from_plane(const vvc355_lmcs_model *mo
 template <int BD, int NL = 64>
 __device__ __forceinline__ void resid_block_add(uint8_t *dst, int dst_stride, const int *res, int w, int h, int joint, int scale, int lane)
 {
-    auto resid_of = [&](int r) {
-        if (joint & 1)
-            r = (r * ((joint & 2) ? -1 : 1)) >> ((joint >> 2) & 1);
-        if (joint & 8) {
-            const int c = clip_intp2(r, BD);
-            r = c > 0 ? (c * scale + (1 << 10)) >> 11 : -((-c * scale + (1 << 10)) >> 11);
-        }
-        return r;
-    };
+    auto resid_of = [&](int r) { return resid_sample<BD>(r, joint, scale); };
     const int n = w * h, lw = ilog2i(w);
     if (w < 4) {
         for (int i = lane; i < n; i += NL) {

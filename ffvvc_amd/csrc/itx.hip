@@ -7,8 +7,10 @@
 // The reference's partial butterflies are wrapping int32 arithmetic, i.e. exactly a dot product with the transform matrix
 // over the inputs its nz gating keeps.  One workgroup owns one transform block: coefficients are staged in LDS, the column
 // pass spreads (column, output row) pairs over the lanes, then the row pass does the same for (row, output column).
+#include <type_traits>
 #include "common.hpp"
 #include "runtime.hpp"
+#include "resid_math.hpp"
 #include "../../include/vvc_mi355.h"
 
 namespace vvc355 {
@@ -223,10 +225,12 @@ __device__ __forceinline__ int4 lv_load4(const vvc355_tb_levels &r, const int16_
 // PACKED: the levels come from the side record `lvr` (groups in `levels`, or int32 at job.coeffs for VVC355_LEVELS_INT32).
 // LFNST: with lf_idx = 1 / 2 the staged block goes through ilfnst_transform (vvc_intra.c:65-127) between the scaling process and the column
 // pass (the intra record path; lf_idx, lf_mode are uniform over the group, w and h are at least 4).
-template <int BD, int NT, int CAP, bool PACKED = false, bool LFNST = false>
+// EPI: with an epilogue type the residual goes sample by sample to epi->sample(x, y, element, residual) instead of to job.coeffs / job.dst
+// (the inter record path's blocks that cannot take the shape-specialised code; such a job has dst = 0 and store_coeffs = 0).
+template <int BD, int NT, int CAP, bool PACKED = false, bool LFNST = false, class EPI = void>
 __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int *buf, int *tmp, const int8_t *cos_lds, int tid,
                                                   const vvc355_tb_levels *lvr = nullptr, const int16_t *levels = nullptr,
-                                                  int lf_idx = 0, int lf_mode = 0)
+                                                  int lf_idx = 0, int lf_mode = 0, EPI *epi = nullptr)
 {
     constexpr bool WAVE = NT <= 64;                  // the group lives inside one wave
     const int w = 1 << job.log2_w, h = 1 << job.log2_h, n = w * h;
@@ -452,6 +456,13 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
             const int o = e0 + q;
             r[q] = o < n ? (sh_final < 0 ? buf[o] : (buf[o] + (1 << (sh_final - 1))) >> sh_final) : 0;
         }
+        if constexpr (!std::is_void<EPI>::value) {
+#pragma unroll
+            for (int q = 0; q < PER; q++)
+                if (e0 + q < n)
+                    epi->sample((e0 + q) & (w - 1), (e0 + q) >> job.log2_w, e0 + q, r[q]);
+            return;
+        }
         if (job.store_coeffs) {
             if (PER < 4) {
 #pragma unroll
@@ -569,228 +580,36 @@ template <int KS> __device__ __forceinline__ void lds_row(const int16_t *p, uint
     }
 }
 
+// Four samples of a row of a plane, as loaded (two per dword above 8 bits, four in one dword at 8 bits), and the add that ends the transform
+template <int BD> __device__ __forceinline__ uint2 px4_load(const uint8_t *p)
+{
+    uint2 v = make_uint2(0, 0);
+    if (BD > 8) v = gld<uint2>(p);
+    else v.x = gld<uint32_t>(p);
+    return v;
+}
+template <int BD> __device__ __forceinline__ void px4_add_store(uint8_t *p, uint2 praw, const int (&res)[4])
+{
+    if (BD > 8) {
+        const int o0 = clip_px<BD>((int)(praw.x & 0xffff) + res[0]), o1 = clip_px<BD>((int)(praw.x >> 16) + res[1]);
+        const int o2 = clip_px<BD>((int)(praw.y & 0xffff) + res[2]), o3 = clip_px<BD>((int)(praw.y >> 16) + res[3]);
+        gst<uint2>(p, make_uint2((uint32_t)o0 | ((uint32_t)o1 << 16), (uint32_t)o2 | ((uint32_t)o3 << 16)));
+    } else {
+        const uint32_t pr = praw.x;
+        const int o0 = clip_px<BD>((int)(pr & 0xff) + res[0]), o1 = clip_px<BD>((int)((pr >> 8) & 0xff) + res[1]);
+        const int o2 = clip_px<BD>((int)((pr >> 16) & 0xff) + res[2]), o3 = clip_px<BD>((int)(pr >> 24) + res[3]);
+        gst<uint32_t>(p, (uint32_t)o0 | ((uint32_t)o1 << 8) | ((uint32_t)o2 << 16) | ((uint32_t)o3 << 24));
+    }
+}
+
 // PACKED: a lane whose tile is coded loads its group (32 bytes, two 16-byte loads; its position is a popcount of the lower mask bits),
 // any other lane loads nothing; jobs with VVC355_LEVELS_INT32 read int32 levels as the plain kernel does.
 template <int BD, int LW, int LH, typename... Lv>
 __global__ __launch_bounds__(256) void itx_shape_kernel(const vvc355_itx_job *__restrict__ jobs, int n_jobs, Lv... lv)
 {
     constexpr bool PACKED = sizeof...(Lv) > 0;
-    using px_t = typename Px<BD>::type;
-    constexpr int W = 1 << LW, H = 1 << LH, CAP = W * H;
-    constexpr int NT = CAP / 16, TBS = 256 / NT;             // lanes per block (one per 4x4 tile), blocks per workgroup
-    using DV = TxDim<H>;                                     // vertical transform: k runs over rows
-    using DH = TxDim<W>;                                     // horizontal transform: k runs over columns
-    constexpr int KVV = DV::KV, PV = DV::P, KSV = DV::KS;
-    constexpr int KVH = DH::KV, PH = DH::P, KSH = DH::KS;
-    constexpr bool WAVE = NT <= 64;
-    constexpr int CT_SZ = KVH * PV, TMP_SZ = H * PH;
-    constexpr int FAST_BYTES = TBS * (CT_SZ + TMP_SZ) * 2, GEN_BYTES = CAP * 8;
-    __shared__ __attribute__((aligned(16))) char lds_raw[FAST_BYTES > GEN_BYTES ? FAST_BYTES : GEN_BYTES];
-    __shared__ __attribute__((aligned(16))) int16_t tab_v[DV::NTYPE * H * PV];
-    __shared__ __attribute__((aligned(16))) int16_t tab_h_own[W == H ? 8 : DH::NTYPE * W * PH];
-    __shared__ int8_t cos_lds[256];
-    const int16_t *tab_h = W == H ? tab_v : tab_h_own;
-
-    DV::stage(tab_v);
-    if (W != H)
-        DH::stage(tab_h_own);
-    cos_lds[threadIdx.x] = d_tab_dct2_cos[threadIdx.x];
-
-    const int sub = threadIdx.x / NT, tid = threadIdx.x % NT;
-    const int wg = xcd_chunked(blockIdx.x, gridDim.x);
-    const int ji = wg * TBS + sub;
-    const bool valid = ji < n_jobs;
-    vvc355_itx_job job = jobs[valid ? ji : n_jobs - 1];
-    resolve_type(job);
-    const int nzw = job.nzw, nzh = job.nzh, range = job.range, bd = job.bd ? job.bd : BD;
-    const int trh = job.trh, trv = job.trv;
-    const int sh_final = 5 + range - bd;
-    bool ok = job.log2_w == LW && job.log2_h == LH && range <= 15 && sh_final >= 1 && trh < DH::NTYPE && trv < DV::NTYPE;
-    const bool dc_only = W == H && trh == TX_DCT2 && trv == TX_DCT2 && nzw == 1 && nzh == 1;
-    const int cntv = dc_only ? 1 : inputs_used(trv, H, nzh);                // rows the column pass reads
-    const int cnt2 = inputs_used(trh, W, nzw);                              // columns the row pass reads
-    ok &= cntv <= KVV && cnt2 <= KVH;
-    const int cnt2r = (cnt2 + KSH - 1) & ~(KSH - 1);
-
-    // this lane's tile for I/O and for the row pass
-    const int y0 = (tid / (W / 4)) * 4, x0 = (tid % (W / 4)) * 4;
-    int *coeffs = (int *)job.coeffs;
-    uint8_t *dst = (uint8_t *)job.dst;
-    const bool act = valid && ok;
-
-    // prediction samples first: they are needed last
-    uint2 praw[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        praw[r] = make_uint2(0, 0);
-        if (act && dst) {
-            const uint8_t *p = dst + row_off(y0 + r, job.dst_stride) + x0 * (int)sizeof(px_t);
-            if (BD > 8) praw[r] = gld<uint2>(p);
-            else praw[r].x = gld<uint32_t>(p);
-        }
-    }
-    int c[4][4];
-    const Dequant dq = itx_job_dequant(job, bd);
-    const bool need = act && y0 < cntv && x0 < nzw && x0 < KVH;
-    unsigned mag = 0;
-    bool packed = false;
-    uint4 pk[2];
-    if constexpr (PACKED) {
-        const LvSrc ls = lv_src(lv...);
-        const vvc355_tb_levels lvr = ls.lv[valid ? ji : n_jobs - 1];
-        packed = !(lvr.flags & VVC355_LEVELS_INT32);
-        const int16_t *g = packed && need ? lv_group(lvr, ls.levels, LW, x0, y0) : nullptr;
-        pk[0] = pk[1] = make_uint4(0, 0, 0, 0);
-        if (g) {
-            pk[0] = gld<uint4>(g);
-            pk[1] = gld<uint4>(g + 8);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        int4 v = make_int4(0, 0, 0, 0);
-        if (PACKED && packed) {
-            if (y0 + r < cntv)
-                v = unpack_i16x4(r & 1 ? make_uint2(pk[r >> 1].z, pk[r >> 1].w) : make_uint2(pk[r >> 1].x, pk[r >> 1].y));
-        } else if (need && y0 + r < cntv) {
-            v = gld<int4>(coeffs + (y0 + r) * W + x0);
-        }
-        if (dq.on) {
-            const unsigned lv = (unsigned)(v.x ^ (v.x >> 31)) | (unsigned)(v.y ^ (v.y >> 31)) | (unsigned)(v.z ^ (v.z >> 31)) | (unsigned)(v.w ^ (v.w >> 31));
-            if ((lv >> 15) == 0) {
-                v.x = dq.apply_small(v.x, x0, y0 + r); v.y = dq.apply_small(v.y, x0 + 1, y0 + r);
-                v.z = dq.apply_small(v.z, x0 + 2, y0 + r); v.w = dq.apply_small(v.w, x0 + 3, y0 + r);
-            } else {
-                v.x = dq.apply(v.x, x0, y0 + r); v.y = dq.apply(v.y, x0 + 1, y0 + r);
-                v.z = dq.apply(v.z, x0 + 2, y0 + r); v.w = dq.apply(v.w, x0 + 3, y0 + r);
-            }
-        }
-        c[r][0] = x0 + 0 < nzw ? v.x : 0; c[r][1] = x0 + 1 < nzw ? v.y : 0;
-        c[r][2] = x0 + 2 < nzw ? v.z : 0; c[r][3] = x0 + 3 < nzw ? v.w : 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            mag |= (unsigned)(c[r][q] ^ (c[r][q] >> 31));
-    }
-    ok &= (mag >> 15) == 0;
-    if (!__syncthreads_and(!valid || ok)) {
-        // some block of this workgroup needs the generic arithmetic: redo them all, one after the other, 256 lanes each
-        int *gbuf = (int *)lds_raw, *gtmp = gbuf + CAP;
-        for (int b = 0; b < TBS; b++) {
-            const int jb = wg * TBS + b;
-            if (jb >= n_jobs)
-                break;
-            vvc355_itx_job jg = jobs[jb];
-            resolve_type(jg);
-            if (jg.log2_w + jg.log2_h <= LW + LH) {
-                if constexpr (PACKED) {
-                    const LvSrc ls = lv_src(lv...);
-                    const vvc355_tb_levels r = ls.lv[jb];
-                    itx_generic_block<BD, 256, CAP, true>(jg, gbuf, gtmp, cos_lds, threadIdx.x, &r, ls.levels);
-                } else
-                    itx_generic_block<BD, 256, CAP>(jg, gbuf, gtmp, cos_lds, threadIdx.x);
-            }
-            __syncthreads();
-        }
-        return;
-    }
-    if (WAVE && !valid)
-        return;                                              // whole groups inside a wave; no workgroup barrier follows
-
-    int16_t *cT = (int16_t *)lds_raw + sub * (CT_SZ + TMP_SZ), *tmp = cT + CT_SZ;
-    if (y0 < KVV && x0 < KVH) {
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            *(uint2 *)&cT[(x0 + q) * PV + y0] = make_uint2(pack_i16(c[0][q], c[1][q]), pack_i16(c[2][q], c[3][q]));
-    }
-    ITX_SYNC();
-
-    // ---- column pass: tile (rows ya.., columns xa..) of tmp, only the columns the row pass reads
-    {
-        constexpr int YT = H / 4;
-        const int xa = (tid / YT) * 4, ya = (tid % YT) * 4;
-        if (xa < cnt2r) {
-            int acc[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) acc[r][q] = 0;
-            if (xa < nzw) {
-                const int16_t *mrow = tab_v + (trv * H + ya) * PV;
-                const int16_t *crow = cT + xa * PV;
-                for (int k = 0; k < cntv; k += KSV) {
-                    uint32_t m[4][KSV / 2], d[4][KSV / 2];
-#pragma unroll
-                    for (int r = 0; r < 4; r++) lds_row<KSV>(mrow + r * PV + k, m[r]);
-#pragma unroll
-                    for (int q = 0; q < 4; q++) lds_row<KSV>(crow + q * PV + k, d[q]);
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-#pragma unroll
-                        for (int q = 0; q < 4; q++)
-#pragma unroll
-                            for (int e = 0; e < KSV / 2; e++) acc[r][q] = dot2_i16(m[r][e], d[q][e], acc[r][q]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                int v[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) v[q] = clip_intp2((acc[r][q] + 64) >> 7, range);
-                *(uint2 *)&tmp[(ya + r) * PH + xa] = make_uint2(pack_i16(v[0], v[1]), pack_i16(v[2], v[3]));
-            }
-        }
-    }
-    ITX_SYNC();
-
-    // ---- row pass on this lane's I/O tile
-    int acc[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) acc[r][q] = 0;
-    {
-        const int16_t *mrow = tab_h + (trh * W + x0) * PH;
-        const int16_t *trow = tmp + y0 * PH;
-        for (int k = 0; k < cnt2; k += KSH) {
-            uint32_t m[4][KSH / 2], d[4][KSH / 2];
-#pragma unroll
-            for (int q = 0; q < 4; q++) lds_row<KSH>(mrow + q * PH + k, m[q]);
-#pragma unroll
-            for (int r = 0; r < 4; r++) lds_row<KSH>(trow + r * PH + k, d[r]);
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-#pragma unroll
-                    for (int e = 0; e < KSH / 2; e++) acc[r][q] = dot2_i16(m[q][e], d[r][e], acc[r][q]);
-        }
-    }
-    if (!valid)
-        return;
-    const int rnd = 1 << (sh_final - 1);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        int res[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) res[q] = (acc[r][q] + rnd) >> sh_final;
-        if (job.store_coeffs)
-            gst<int4>(coeffs + (y0 + r) * W + x0, make_int4(res[0], res[1], res[2], res[3]));
-        if (dst) {
-            uint8_t *p = dst + row_off(y0 + r, job.dst_stride) + x0 * (int)sizeof(px_t);
-            if (BD > 8) {
-                const int o0 = clip_px<BD>((int)(praw[r].x & 0xffff) + res[0]), o1 = clip_px<BD>((int)(praw[r].x >> 16) + res[1]);
-                const int o2 = clip_px<BD>((int)(praw[r].y & 0xffff) + res[2]), o3 = clip_px<BD>((int)(praw[r].y >> 16) + res[3]);
-                gst<uint2>(p, make_uint2((uint32_t)o0 | ((uint32_t)o1 << 16), (uint32_t)o2 | ((uint32_t)o3 << 16)));
-            } else {
-                const uint32_t pr = praw[r].x;
-                const int o0 = clip_px<BD>((int)(pr & 0xff) + res[0]), o1 = clip_px<BD>((int)((pr >> 8) & 0xff) + res[1]);
-                const int o2 = clip_px<BD>((int)((pr >> 16) & 0xff) + res[2]), o3 = clip_px<BD>((int)(pr >> 24) + res[3]);
-                gst<uint32_t>(p, (uint32_t)o0 | ((uint32_t)o1 << 8) | ((uint32_t)o2 << 16) | ((uint32_t)o3 << 24));
-            }
-        }
-    }
+#include "itx_shape_body.inc"
 }
-#undef ITX_SYNC
 
 // vvc355_levels_expand: one wave per job, lanes over the 4-sample row segments of the job's nzw x nzh window.  A segment is 8 bytes of one
 // group (slots outside a block narrower than 4 are zero in the stream, and no store reaches past nzw <= w).
@@ -1158,6 +977,227 @@ static void launch_intra_tb(hipStream_t st, const vvc355_intra_tb_frame *fd, con
     if (wgs[4]) hipLaunchKernelGGL((intra_tb_kernel<256, 4096, PACKED>), dim3(wgs[4]), dim3(256), 0, st, fd, cf[4], cf[5]);
 }
 
+// ------------------------------------------------------------------------------------------------ inter transform stage from records
+//
+// vvc355_inter_tb_pass: the records of one shape bin go through the shape-specialised body (itx_shape_body.inc), the job made in registers
+// from the 16-byte vvc355_inter_tu (what itx_build_kernel writes to memory), the residual added from the registers the row pass leaves
+// it in: plain, through the 64x64 unit's chroma scale, to both chroma planes of a joint transform unit, or stored to the arena (KEEP).
+template <int BD> struct InterEpi {
+    uint8_t *dst0, *dst1;                            // the block in its own plane; in plane 3 - c_idx for a joint record, else null
+    int stride0, stride1;
+    int *keep;                                       // the arena slot of a KEEP record, else null
+    int joint, scale;
+    uint2 p0[4], p1[4];
+    static constexpr int PXS = (int)sizeof(typename Px<BD>::type);
+    __device__ __forceinline__ void prefetch(bool act, int x0, int y0)
+    {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            p0[r] = p1[r] = make_uint2(0, 0);
+            if (act && !keep) {
+                p0[r] = px4_load<BD>(dst0 + row_off(y0 + r, stride0) + x0 * PXS);
+                if (dst1)
+                    p1[r] = px4_load<BD>(dst1 + row_off(y0 + r, stride1) + x0 * PXS);
+            }
+        }
+    }
+    template <int W> __device__ __forceinline__ void row(int r, int x0, int y, const int (&res)[4])
+    {
+        if (keep) {
+            gst<int4>(keep + y * W + x0, make_int4(res[0], res[1], res[2], res[3]));
+            return;
+        }
+        int own[4], other[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            own[q] = resid_sample<BD>(res[q], joint & 8, scale);
+            other[q] = resid_sample<BD>(res[q], joint, scale);
+        }
+        px4_add_store<BD>(dst0 + row_off(y, stride0) + x0 * PXS, p0[r], own);
+        if (dst1)
+            px4_add_store<BD>(dst1 + row_off(y, stride1) + x0 * PXS, p1[r], other);
+    }
+    // itx_generic_block's hook: thin blocks, and the workgroups that fall back to the generic arithmetic
+    __device__ __forceinline__ void sample(int x, int y, int o, int r)
+    {
+        if (keep) {
+            gst<int>(keep + o, r);
+            return;
+        }
+        uint8_t *row0 = dst0 + row_off(y, stride0);
+        st_px<BD>(row0, x, clip_px<BD>(ld_px<BD>(row0, x) + resid_sample<BD>(r, joint & 8, scale)));
+        if (dst1) {
+            uint8_t *row1 = dst1 + row_off(y, stride1);
+            st_px<BD>(row1, x, clip_px<BD>(ld_px<BD>(row1, x) + resid_sample<BD>(r, joint, scale)));
+        }
+    }
+};
+
+// what the kernels read of vvc355_inter_tb_frame: everything in front of bin_first (the launches are the host's)
+struct InterTbHead {
+    uint64_t tus, coeffs, lv, levels, plane[3], scale_table;
+    int32_t  stride[3], width, height, n_tus;
+    uint8_t  hs, vs, size_y, range, bd, pad_[3];
+};
+static_assert(sizeof(InterTbHead) == offsetof(vvc355_inter_tb_frame, bin_first) && offsetof(InterTbHead, hs) == offsetof(vvc355_inter_tb_frame, hs) &&
+              offsetof(InterTbHead, stride) == offsetof(vvc355_inter_tb_frame, stride), "InterTbHead is the frame without bin_first");
+
+// Records [first, ...) of bin `bin` of channel type `ch`; (lw0, lh0) the bin's shape (what a skipped record's stand-in job gets).
+//   get(i, job, epi)        record i as a job (types resolved) and its epilogue; false = the record is skipped (the job is then a harmless one
+//                           of the bin's shape: nothing is read or written for it)
+//   levels_of(i), stream()  the block's side record (an int32 one when the picture has no packed levels) and the level stream
+template <int BD> struct InterTbSrc {
+    using Epi = InterEpi<BD>;
+    InterTbHead f;
+    int first, ch, bin, lw0, lh0;
+    __device__ __forceinline__ vvc355_tb_levels levels_of(int i) const
+    {
+        if (!f.lv)
+            return vvc355_tb_levels{ 0, 0, VVC355_LEVELS_INT32 };
+        const uint4 v = gld<uint4>((const vvc355_tb_levels *)f.lv + first + i);
+        return vvc355_tb_levels{ (uint64_t)v.x | ((uint64_t)v.y << 32), v.z, v.w };
+    }
+    __device__ __forceinline__ const int16_t *stream() const { return (const int16_t *)f.levels; }
+    __device__ __forceinline__ bool get(int i, vvc355_itx_job &job, Epi &epi) const
+    {
+        vvc355_inter_tu t;
+        const uint4 raw = gld<uint4>((const vvc355_inter_tu *)f.tus + first + i);
+        __builtin_memcpy(&t, &raw, sizeof(t));
+        const int lw = t.log2_w, lh = t.log2_h, c = t.flags & 3, joint = t.joint_mts & 15, mts = (t.joint_mts >> 4) & 7;
+        const bool keep = t.flags & VVC355_INTER_TU_KEEP;
+        // contract violations are skipped, never executed: the shape bounds the LDS tiles and the arena slot, the rectangle the pixel
+        // accesses, 4 elements are the unit of the vector loads, the unit indexes the scale table
+        bool ok = lw <= 6 && lh <= 6 && lw + lh >= 2 && ((lw >= 2 && lh >= 2) ? (lw - 2) * 5 + (lh - 2) : 25) == bin;
+        ok &= !(t.flags & 0xc0) && !(t.joint_mts & 0x80) && mts <= 4 && c != 3 && (c != 0) == (ch != 0) && !(c == 0 && joint);
+        ok &= !((joint & 8) && !f.scale_table);
+        const int hs = c ? f.hs : 0, vs = c ? f.vs : 0;
+        ok &= t.x0 >= 0 && t.y0 >= 0 && t.x0 + (1 << (lw & 7)) <= (f.width >> hs) && t.y0 + (1 << (lh & 7)) <= (f.height >> vs);
+        if (keep || (levels_of(i).flags & VVC355_LEVELS_INT32))
+            ok &= !(t.coeff_off & 3);
+        int scale = 0;
+        if (ok && (joint & 8)) {
+            // the unit of (cu->x0, cu->y0): the block's own unit minus the record's two bits
+            const int ls = f.size_y == 64 ? 6 : 5;
+            const int ux = ((t.x0 << hs) >> ls) - ((t.flags >> 4) & 1), uy = ((t.y0 << vs) >> ls) - ((t.flags >> 5) & 1);
+            ok = ux >= 0 && uy >= 0;
+            if (ok)
+                scale = (int)gld<int16_t>((const int16_t *)f.scale_table + uy * ((f.width + (1 << ls) - 1) >> ls) + ux);
+        }
+        job = {};
+        job.log2_w = (uint8_t)(ok ? lw : lw0); job.log2_h = (uint8_t)(ok ? lh : lh0);
+        job.nzw = job.nzh = 1;
+        job.range = f.range; job.bd = f.bd;
+        job.log2_matrix_size = 1; job.dc = -1;
+        epi.dst0 = epi.dst1 = nullptr;
+        epi.keep = nullptr;
+        epi.stride0 = epi.stride1 = 0;
+        epi.joint = epi.scale = 0;
+        if (!ok)
+            return false;
+        job.coeffs = f.coeffs + (uint64_t)t.coeff_off * 4;
+        job.nzw = (uint8_t)min((int)t.nzw, 1 << lw); job.nzh = (uint8_t)min((int)t.nzh, 1 << lh);
+        job.dq_flags = (uint8_t)(1 | ((t.flags & VVC355_INTER_TU_DEP_QUANT) ? 2 : 0)); job.dq_qp = t.qp;
+        job.mts_flags = VVC355_ITX_DERIVE_TYPE; job.tu_flags = t.tu_flags; job.mts_idx = (uint8_t)mts; job.c_idx = (uint8_t)c;
+        resolve_type(job);
+        if (((lw < 2 || lw > 5) && job.trh) || ((lh < 2 || lh > 5) && job.trv)) {       // DST-7 / DCT-8 exist for 4..32 points only
+            job.trh = job.trv = 0;
+            return false;
+        }
+        // (picked between values, not between members: a conditional of lvalues is a conditional of addresses)
+        const uint64_t p0 = f.plane[0], p1 = f.plane[1], p2 = f.plane[2];
+        const int s0 = f.stride[0], s1 = f.stride[1], s2 = f.stride[2];
+        const uint64_t plane = c == 0 ? p0 : c == 1 ? p1 : p2, other = c == 1 ? p2 : p1;
+        const int stride = c == 0 ? s0 : c == 1 ? s1 : s2, ostride = c == 1 ? s2 : s1;
+        if (keep) {
+            epi.keep = (int *)job.coeffs;
+            return true;
+        }
+        epi.dst0 = (uint8_t *)plane + row_off(t.y0, stride) + t.x0 * Epi::PXS;
+        epi.stride0 = stride;
+        if (joint & 1) {
+            epi.dst1 = (uint8_t *)other + row_off(t.y0, ostride) + t.x0 * Epi::PXS;
+            epi.stride1 = ostride;
+        }
+        epi.joint = joint;
+        epi.scale = scale;
+        return true;
+    }
+};
+
+template <int BD, int LW, int LH>
+__global__ __launch_bounds__(256) void inter_tb_shape_kernel(const vvc355_inter_tb_frame *__restrict__ fp, int first, int end, int ch)
+{
+    constexpr bool PACKED = true;                    // a picture without packed levels has int32 side records made up by the source
+    const InterTbSrc<BD> src{ load_uniform((const InterTbHead *)fp), first, ch, (LW - 2) * 5 + (LH - 2), LW, LH };
+    const int n_jobs = end - first;
+#define ITX_SHAPE_RECORDS
+#include "itx_shape_body.inc"
+#undef ITX_SHAPE_RECORDS
+}
+#undef ITX_SYNC
+
+// bin 25, blocks with a side of 1 or 2 (at most 128 coefficients): a wave per block through the generic code
+template <int BD>
+__global__ __launch_bounds__(256) void inter_tb_thin_kernel(const vvc355_inter_tb_frame *__restrict__ fp, int first, int end, int ch)
+{
+    __shared__ __attribute__((aligned(16))) int buf_all[4 * 256];
+    __shared__ __attribute__((aligned(16))) int tmp_all[4 * 256];
+    __shared__ int8_t cos_lds[256];
+    cos_lds[threadIdx.x] = d_tab_dct2_cos[threadIdx.x];
+    __syncthreads();
+    const int sub = threadIdx.x >> 6, tid = threadIdx.x & 63;
+    const int i = xcd_chunked(blockIdx.x, gridDim.x) * 4 + sub;
+    if (i >= end - first)
+        return;                                      // whole waves leave together
+    const InterTbSrc<BD> src{ load_uniform((const InterTbHead *)fp), first, ch, 25, 1, 1 };
+    vvc355_itx_job job;
+    InterEpi<BD> epi;
+    if (!src.get(i, job, epi))
+        return;
+    const vvc355_tb_levels r = src.levels_of(i);
+    itx_generic_block<BD, 64, 256, true, false, InterEpi<BD>>(job, buf_all + sub * 256, tmp_all + sub * 256, cos_lds, tid, &r, src.stream(), 0, 0, &epi);
+}
+
+template <int BD, int LW>
+static void launch_inter_tb_shape(hipStream_t st, const vvc355_inter_tb_frame *fd, int first, int end, int ch, int log2_h)
+{
+#define VVC355_INTER_TB_SHAPE(LH)                                                                                     \
+    case LH: {                                                                                                        \
+        constexpr int TBS = 256 / ((1 << (LW + LH)) / 16);                                                            \
+        hipLaunchKernelGGL((inter_tb_shape_kernel<BD, LW, LH>), dim3((end - first + TBS - 1) / TBS), dim3(256), 0, st, fd, first, end, ch); \
+    } break;
+    switch (log2_h) {
+    VVC355_INTER_TB_SHAPE(2) VVC355_INTER_TB_SHAPE(3) VVC355_INTER_TB_SHAPE(4) VVC355_INTER_TB_SHAPE(5) VVC355_INTER_TB_SHAPE(6)
+    }
+#undef VVC355_INTER_TB_SHAPE
+}
+
+// one launch per non-empty bin of the requested channel types
+template <int BD>
+static void launch_inter_tb(hipStream_t st, const vvc355_inter_tb_frame *fd, const vvc355_inter_tb_frame &fh, int channels)
+{
+    for (int ch = 0; ch < 2; ch++) {
+        if (!(channels & (1 << ch)))
+            continue;
+        for (int bin = 0; bin < VVC355_INTER_TB_BINS; bin++) {
+            const int first = fh.bin_first[ch][bin], end = fh.bin_first[ch][bin + 1];
+            if (end <= first)
+                continue;
+            if (bin == 25) {
+                hipLaunchKernelGGL((inter_tb_thin_kernel<BD>), dim3((end - first + 3) / 4), dim3(256), 0, st, fd, first, end, ch);
+                continue;
+            }
+            switch (bin / 5 + 2) {
+            case 2: launch_inter_tb_shape<BD, 2>(st, fd, first, end, ch, bin % 5 + 2); break;
+            case 3: launch_inter_tb_shape<BD, 3>(st, fd, first, end, ch, bin % 5 + 2); break;
+            case 4: launch_inter_tb_shape<BD, 4>(st, fd, first, end, ch, bin % 5 + 2); break;
+            case 5: launch_inter_tb_shape<BD, 5>(st, fd, first, end, ch, bin % 5 + 2); break;
+            case 6: launch_inter_tb_shape<BD, 6>(st, fd, first, end, ch, bin % 5 + 2); break;
+            }
+        }
+    }
+}
+
 } // namespace vvc355
 
 using namespace vvc355;
@@ -1209,6 +1249,38 @@ int vvc355_intra_tb_pass(void *stream, const vvc355_intra_tb_frame *frame_dev, c
         launch_intra_tb<true>((hipStream_t)stream, frame_dev, *frame_host, mode);
     else
         launch_intra_tb<false>((hipStream_t)stream, frame_dev, *frame_host, mode);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int vvc355_inter_tb_pass(void *stream, const vvc355_inter_tb_frame *frame_dev, const vvc355_inter_tb_frame *frame_host, int channels)
+{
+    // the host copy is checked before any HIP call: a refused frame launches nothing
+    const vvc355_inter_tb_frame *f = frame_host;
+    if (!f || f->n_tus < 0 || f->bin_first[0][0] != 0 || f->bin_first[0][VVC355_INTER_TB_BINS] != f->bin_first[1][0] ||
+        f->bin_first[1][VVC355_INTER_TB_BINS] != f->n_tus)
+        return VVC355_INTER_TB_E_BINS;
+    for (int ch = 0; ch < 2; ch++)
+        for (int k = 0; k < VVC355_INTER_TB_BINS; k++)
+            if (f->bin_first[ch][k] > f->bin_first[ch][k + 1])
+                return VVC355_INTER_TB_E_BINS;
+    if (f->bd != 8 && f->bd != 10 && f->bd != 12)
+        return VVC355_INTER_TB_E_BD;
+    if (f->range < 15 || f->range > 20)
+        return VVC355_INTER_TB_E_RANGE;
+    if (!f->lv != !f->levels)
+        return VVC355_INTER_TB_E_LEVELS;
+    if (f->scale_table && f->size_y != 32 && f->size_y != 64)
+        return VVC355_INTER_TB_E_SIZE_Y;
+    if (f->hs > 1 || f->vs > 1)
+        return VVC355_INTER_TB_E_SHIFT;
+    if (channels < 1 || channels > 3)
+        return VVC355_INTER_TB_E_CHANNELS;
+    if (channels == 3 && f->scale_table)
+        return VVC355_INTER_TB_E_ORDER;
+    if (f->n_tus == 0)
+        return 0;
+    VVC355_BD_DISPATCH(f->bd, launch_inter_tb<BD>((hipStream_t)stream, frame_dev, *f, channels));
     HIP_CHECK(hipGetLastError());
     return 0;
 }

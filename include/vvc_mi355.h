@@ -418,6 +418,75 @@ enum { VVC355_INTRA_TB_E_CLASS = -1, VVC355_INTRA_TB_E_BD = -2, VVC355_INTRA_TB_
 int vvc355_intra_tb_pass(void *stream, const vvc355_intra_tb_frame *frame_dev, const vvc355_intra_tb_frame *frame_host);
 
 /*
+ * The transform stage of every coding unit the in-order pass does not own (the inter coding units) from one 16-byte record per coded
+ * transform block: the TU loop of itransform (vvc_intra.c:441-476) as dequant -> derive_transform_type (:130-164) -> itx -> the tail
+ * (lmcs_scale_chroma :468-469, add_residual :472, add_residual_for_joint_coding_chroma :166-186) in one kernel per block.  No job array
+ * (vvc355_itx_job, vvc355_lmcs_resid_job) is built and the scaled chroma residual never visits the arena: the kernel makes its job in
+ * registers and adds the residual, scaled when asked, from the registers the transform left it in.  Transform skip, BDPCM and scaling
+ * lists are NOT covered: such blocks stay with vvc355_dequant_batch and the residual entries.
+ *
+ *   coeff_off   the block's slot in the arena, int32 elements, a multiple of 4: its int32 levels when the block is not packed, and its
+ *               residual OUTPUT when KEEP is set; unused (and unchecked) otherwise
+ *   x0, y0      position in the component's samples; nzw, nzh = max_scan_x + 1, max_scan_y + 1 (clamped to the block)
+ *   qp          tb->qp; tu_flags = VVC355_TU_* of THIS block's coding unit (and SPS): SBT and explicit MTS differ from unit to unit
+ *   flags       bits 0-1 c_idx; bit 2 sh_dep_quant_used_flag; bit 3 KEEP: transform only — the residual goes to the arena slot and the
+ *               picture is not touched (blocks whose add stays with the in-order pass; vvc355_itx_tu.flags bit 2);
+ *               bits 4 / 5: the 64x64 unit (size_y) that holds the block minus the unit that holds its coding unit's origin, per axis
+ *               (x / y; 0 or 1: a coding unit of 128 luma samples spans two units, and lmcs_scale_chroma takes the scale of
+ *               (cu->x0, cu->y0), vvc_intra.c:469 -> vvc_intra_template.c:397-398); read with joint bit 3 only; bits 6-7 reserved, 0
+ *   joint_mts   bits 0-3 with the meaning of vvc355_recon_cmd.joint: bit 0 the transform unit has tu_joint_cbcr_residual_flag, bit 1
+ *               negative sign (ph_joint_cbcr_sign_flag), bit 2 shift (coded_flag[1] ^ coded_flag[2]), bit 3 chroma residual scaling
+ *               (itransform's chroma_scale, :449; the host decides it as for the RESID command); bits 4-6 cu->mts_idx (0..4); bit 7 reserved
+ * A joint transform unit is ONE record, the coded block (c_idx 1 or 2): the residual is added to its own plane and the sign / shift form
+ * to plane 3 - c_idx at the same position, both through the scale when bit 3 is set.  One transform, two adds.
+ *
+ * Record order: luma records first, then chroma, and inside a channel type GROUPED BY SHAPE BIN: bin (log2_w - 2) * 5 + (log2_h - 2) for the
+ * 25 shapes with both sides 4..64, bin 25 for blocks with a side of 1 or 2.  Records [bin_first[ch][k], bin_first[ch][k + 1]) are bin k of
+ * channel type ch, so bin_first[0][0] = 0, bin_first[0][26] = bin_first[1][0] and bin_first[1][26] = n_tus.  Grouping is the host's job, as
+ * it is for vvc355_itx_frame_build.  lv[i] belongs to tus[i].
+ *
+ * A record that breaks the contract is SKIPPED, nothing is read or written for it: a shape that is not its bin's, a side beyond 64, fewer
+ * than 4 coefficients, reserved bits, mts_idx above 4, c_idx 3, c_idx 0 with joint bits, c_idx of the other channel type, joint bit 3 with
+ * scale_table == 0 or a unit left of / above the picture, a rectangle not inside its plane (for a joint record: either plane), coeff_off
+ * not a multiple of 4 where it is used, a transform other than DCT-2 along a side of 1, 2 or 64 (DST-7 / DCT-8 exist for 4..32 points).
+ */
+typedef struct vvc355_inter_tu {
+    uint32_t coeff_off;
+    int16_t  x0, y0;
+    uint8_t  log2_w, log2_h, nzw, nzh;
+    uint8_t  qp, tu_flags, flags, joint_mts;
+} vvc355_inter_tu;
+enum { VVC355_INTER_TU_DEP_QUANT = 4, VVC355_INTER_TU_KEEP = 8, VVC355_INTER_TU_UNIT_DX = 16, VVC355_INTER_TU_UNIT_DY = 32 };
+enum { VVC355_INTER_TB_BINS = 26 };
+
+typedef struct vvc355_inter_tb_frame {
+    uint64_t tus;              /* DEVICE vvc355_inter_tu[n_tus], ordered as bin_first says */
+    uint64_t coeffs;           /* DEVICE int32 arena: levels of unpacked blocks, residuals of KEEP blocks */
+    uint64_t lv, levels;       /* DEVICE vvc355_tb_levels[n_tus] paired by index + the int16 group stream; both 0 = int32 levels in place at coeff_off */
+    uint64_t plane[3];         /* DEVICE: sample (0, 0) of each component */
+    uint64_t scale_table;      /* DEVICE int16: vvc355_lmcs_scale_frame.scale as vvc355_lmcs_vpdu_scale_pass left it; 0 = no record may set joint bit 3 */
+    int32_t  stride[3];        /* bytes */
+    int32_t  width, height;    /* luma picture size */
+    int32_t  n_tus;
+    uint8_t  hs, vs;           /* chroma shifts, 0 or 1 */
+    uint8_t  size_y;           /* min(CtbSizeY, 64): 32 or 64; read with scale_table only */
+    uint8_t  range, bd;        /* log2_transform_range 15..20; bit depth 8 / 10 / 12 */
+    uint8_t  pad_[3];
+    int32_t  bin_first[2][VVC355_INTER_TB_BINS + 1];
+} vvc355_inter_tb_frame;
+
+/* what vvc355_inter_tb_pass returns for a frame it refuses: bin_first not non-decreasing from 0 to n_tus through both channel types (or
+ * n_tus < 0, or no frame); bd not 8 / 10 / 12; range outside 15..20; only one of lv / levels set; size_y not 32 / 64 with a scale table;
+ * hs or vs above 1; channels outside 1..3; channels == 3 with a scale table (the table is made from the luma this stage reconstructs) */
+enum { VVC355_INTER_TB_E_BINS = -1, VVC355_INTER_TB_E_BD = -2, VVC355_INTER_TB_E_RANGE = -3, VVC355_INTER_TB_E_LEVELS = -4,
+       VVC355_INTER_TB_E_SIZE_Y = -5, VVC355_INTER_TB_E_SHIFT = -6, VVC355_INTER_TB_E_CHANNELS = -7, VVC355_INTER_TB_E_ORDER = -8 };
+/* Runs the stage on `stream` for the channel types in `channels` (1 luma, 2 chroma, 3 both): one launch per non-empty bin.  A picture
+ * with chroma residual scaling calls it with 1, then vvc355_lmcs_vpdu_scale_pass (it reads the luma this call reconstructed), then with 2.
+ * The host copy of the frame is checked before any HIP call.
+ * returns 0, or a negative VVC355_INTER_TB_E_* with NOTHING launched */
+int vvc355_inter_tb_pass(void *stream, const vvc355_inter_tb_frame *frame_dev, const vvc355_inter_tb_frame *frame_host, int channels);
+
+/*
  * Scaling process for transform coefficients (dequant) — NOT a table slot in the reference: host C in
  * vvc_intra.c:277-417 (derive_qp :277, derive_scale :311, derive_scale_m :341, scale_coeff :391, dequant :400),
  * called per transform block right before LFNST / itx (vvc_intra.c:455-462).  Flattened: everything read through
