@@ -156,6 +156,8 @@ BATCH_SIGNATURES = {
     "intra_tb_pass":    ("i", "ppp"),
     # the transform stage of the other coding units from 16-byte records (vvc355_inter_tu): transform + (scaled, joint) residual add
     "inter_tb_pass":    ("i", "pppi"),
+    # the transform-skip / BDPCM blocks from 16-byte records (vvc355_ts_tu): BDPCM on the levels + scaling + (scaled, joint) residual add
+    "ts_tb_pass":       ("i", "pppi"),
 }
 
 
@@ -593,6 +595,29 @@ class InterTbFrame(ctypes.Structure):
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_tus", ctypes.c_int32),
                 ("hs", ctypes.c_uint8), ("vs", ctypes.c_uint8), ("size_y", ctypes.c_uint8), ("range", ctypes.c_uint8), ("bd", ctypes.c_uint8),
                 ("pad_", ctypes.c_uint8 * 3), ("bin_first", (ctypes.c_int32 * (INTER_TB_BINS + 1)) * 2)]
+
+
+class TsTu(ctypes.Structure):
+    """Mirror of vvc355_ts_tu (one coded transform-skip block, BDPCM included)."""
+    _fields_ = [("coeff_off", ctypes.c_uint32), ("x0", ctypes.c_int16), ("y0", ctypes.c_int16),
+                ("log2_w", ctypes.c_uint8), ("log2_h", ctypes.c_uint8), ("nzw", ctypes.c_uint8), ("nzh", ctypes.c_uint8),
+                ("qp", ctypes.c_uint8), ("pad_", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("joint", ctypes.c_uint8)]
+
+
+# vvc355_ts_tu.flags: bits 0-1 c_idx, then these; joint = bits 0-3 of vvc355_recon_cmd.joint
+TS_TU_BDPCM, TS_TU_KEEP, TS_TU_UNIT_DX, TS_TU_UNIT_DY, TS_TU_VERTICAL = 4, 8, 16, 32, 64
+TS_TB_CLASSES = 4
+(TS_TB_E_CLASS, TS_TB_E_BD, TS_TB_E_RANGE, TS_TB_E_LEVELS, TS_TB_E_SIZE_Y, TS_TB_E_SHIFT, TS_TB_E_CHANNELS,
+ TS_TB_E_ORDER) = -1, -2, -3, -4, -5, -6, -7, -8
+
+
+class TsTbFrame(ctypes.Structure):
+    """Mirror of vvc355_ts_tb_frame."""
+    _fields_ = [("tus", ctypes.c_uint64), ("coeffs", ctypes.c_uint64), ("lv", ctypes.c_uint64), ("levels", ctypes.c_uint64),
+                ("plane", ctypes.c_uint64 * 3), ("scale_table", ctypes.c_uint64), ("stride", ctypes.c_int32 * 3),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_tus", ctypes.c_int32),
+                ("hs", ctypes.c_uint8), ("vs", ctypes.c_uint8), ("size_y", ctypes.c_uint8), ("range", ctypes.c_uint8), ("bd", ctypes.c_uint8),
+                ("pad_", ctypes.c_uint8 * 3), ("class_first", (ctypes.c_int32 * (TS_TB_CLASSES + 1)) * 2)]
 
 
 class ItxFrame(ctypes.Structure):

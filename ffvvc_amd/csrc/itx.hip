@@ -1198,6 +1198,279 @@ static void launch_inter_tb(hipStream_t st, const vvc355_inter_tb_frame *fd, con
     }
 }
 
+// ------------------------------------------------------------------------------------------------ transform-skip blocks from records
+//
+// vvc355_ts_tb_pass: what itransform does for a block with tb->ts (vvc_intra.c:455-475) — transform_bdpcm on the levels, the scaling
+// process with ts = 1, no transform, the tail — from one 16-byte vvc355_ts_tu.  A lane owns one 4x4 tile of its block (the unit of the
+// packed level stream, bit `tile` of the side record's mask) in 16 registers; NT lanes, one per tile of the largest block of the area
+// class, form a group inside one wave.  Nothing is staged in LDS and no job array exists.
+
+// what the kernel reads of vvc355_ts_tb_frame: everything in front of class_first (the grid is the host's)
+struct TsTbHead {
+    uint64_t tus, coeffs, lv, levels, plane[3], scale_table;
+    int32_t  stride[3], width, height, n_tus;
+    uint8_t  hs, vs, size_y, range, bd, pad_[3];
+};
+static_assert(sizeof(TsTbHead) == offsetof(vvc355_ts_tb_frame, class_first) && offsetof(TsTbHead, hs) == offsetof(vvc355_ts_tb_frame, hs) &&
+              offsetof(TsTbHead, stride) == offsetof(vvc355_ts_tb_frame, stride), "TsTbHead is the frame without class_first");
+
+// one channel type's four area classes in one grid: class k owns the workgroups [wg_first[k - 1], wg_first[k]) (class 0 those below
+// wg_first[0]) and the records [first[k], first[k + 1])
+struct TsTbGrid {
+    int wg_first[4];
+    int first[5];
+};
+
+// transform_bdpcm (vvcdsp_template.c:76) along the second index of v: line l of the tile holds a[0..3], the tile is number `pos` of its
+// line of tiles, the tile before it belongs to lane - stride.  Every step is x -> clip(x + a), and steps compose into
+// x -> clamp(x + s, lo, hi), so a tile is one such triple and the carry walks the at most MAXP tiles of a line exactly, saturation
+// included.  The first sample of a line is taken as it is (the reference starts at the second).
+template <int MAXP>
+__device__ __forceinline__ void ts_bdpcm_lines(int (&v)[4][4], int pos, int stride, int range)
+{
+    const int lane = threadIdx.x & 63;
+    int s[4], lo[4], hi[4], out[4], cin[4];
+#pragma unroll
+    for (int l = 0; l < 4; l++) {
+        s[l] = out[l] = v[l][0];
+        lo[l] = -(1 << range); hi[l] = (1 << range) - 1;
+        cin[l] = 0;
+#pragma unroll
+        for (int k = 1; k < 4; k++) {
+            s[l] += v[l][k];
+            lo[l] = clip_intp2(lo[l] + v[l][k], range); hi[l] = clip_intp2(hi[l] + v[l][k], range);
+            out[l] = clip_intp2(out[l] + v[l][k], range);       // the line's last sample when the tile is its first
+        }
+    }
+#pragma unroll
+    for (int p = 1; p < MAXP; p++) {
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+            const int prev = __shfl(out[l], lane - stride);
+            if (pos == p) {
+                cin[l] = prev;
+                out[l] = clip3(prev + s[l], lo[l], hi[l]);
+            }
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 4; l++) {
+        int x = pos ? clip_intp2(cin[l] + v[l][0], range) : v[l][0];
+        v[l][0] = x;
+#pragma unroll
+        for (int k = 1; k < 4; k++)
+            v[l][k] = x = clip_intp2(x + v[l][k], range);
+    }
+}
+
+__device__ __forceinline__ void ts_transpose(int (&v)[4][4])
+{
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int q = r + 1; q < 4; q++) {
+            const int a = v[r][q];
+            v[r][q] = v[q][r];
+            v[q][r] = a;
+        }
+}
+
+// Record wg * (256 / NT) + threadIdx.x / NT of [first, end), an area class of at most 1 << CAPLOG2 samples, of channel type ch.
+template <int BD, int NT, int CAPLOG2>
+__device__ __forceinline__ void ts_tb_group(const TsTbHead &f, int first, int end, int wg, int ch)
+{
+    constexpr int PXS = (int)sizeof(typename Px<BD>::type);
+    constexpr int MAXP = NT < 8 ? NT : 8;            // tiles along a side: a side is at most 32
+    const int tile = threadIdx.x % NT;
+    const int i = first + wg * (256 / NT) + threadIdx.x / NT;
+    if (i >= end)
+        return;                                      // whole groups leave together
+    vvc355_ts_tu t;
+    const uint4 raw = gld<uint4>((const vvc355_ts_tu *)f.tus + i);
+    __builtin_memcpy(&t, &raw, sizeof(t));
+    vvc355_tb_levels r = { 0, 0, VVC355_LEVELS_INT32 };
+    if (f.lv) {
+        const uint4 q = gld<uint4>((const vvc355_tb_levels *)f.lv + i);
+        r = vvc355_tb_levels{ (uint64_t)q.x | ((uint64_t)q.y << 32), q.z, q.w };
+    }
+    const bool packed = !(r.flags & VVC355_LEVELS_INT32);
+    const int lw = t.log2_w, lh = t.log2_h, c = t.flags & 3, joint = t.joint & 15;
+    const bool keep = t.flags & VVC355_TS_TU_KEEP;
+    // contract violations are skipped, never executed: the area bounds the group's tiles and the arena slot, the rectangle the pixel
+    // accesses, 4 elements are the unit of the vector accesses, the unit indexes the scale table
+    bool ok = lw >= 1 && lw <= 5 && lh >= 1 && lh <= 5 && lw + lh >= 3 && lw + lh <= CAPLOG2;
+    ok &= !(t.flags & 0x80) && !(t.joint & 0xf0) && !t.pad_ && c != 3 && (c != 0) == (ch != 0) && !(c == 0 && joint);
+    ok &= !((joint & 8) && !f.scale_table);
+    const int hs = c ? f.hs : 0, vs = c ? f.vs : 0;
+    ok &= t.x0 >= 0 && t.y0 >= 0 && t.x0 + (1 << (lw & 7)) <= (f.width >> hs) && t.y0 + (1 << (lh & 7)) <= (f.height >> vs);
+    if (keep || !packed)
+        ok &= !(t.coeff_off & 3);
+    int scale = 0;
+    if (ok && (joint & 8)) {
+        // the unit of (cu->x0, cu->y0): the block's own unit minus the record's two bits
+        const int ls = f.size_y == 64 ? 6 : 5;
+        const int ux = ((t.x0 << hs) >> ls) - ((t.flags >> 4) & 1), uy = ((t.y0 << vs) >> ls) - ((t.flags >> 5) & 1);
+        ok = ux >= 0 && uy >= 0;
+        if (ok)
+            scale = (int)gld<int16_t>((const int16_t *)f.scale_table + uy * ((f.width + (1 << ls) - 1) >> ls) + ux);
+    }
+    if (!ok)
+        return;
+
+    const int w = 1 << lw, h = 1 << lh, ltw = max(lw - 2, 0), tw = 1 << ltw, th = 1 << max(lh - 2, 0);
+    const int gx = tile & (tw - 1), gy = tile >> ltw, x0 = gx * 4, y0 = gy * 4;
+    const bool act = tile < tw * th;                 // idle lanes stay for the shuffles of the scan
+    const int rows = act ? min(4, h - y0) : 0;       // of the tile inside the block; its columns: 4, or 2 when w is 2
+
+    // (picked between values, not between members: a conditional of lvalues is a conditional of addresses)
+    const uint64_t pl0 = f.plane[0], pl1 = f.plane[1], pl2 = f.plane[2];
+    const int s0 = f.stride[0], s1 = f.stride[1], s2 = f.stride[2];
+    const int stride = c == 0 ? s0 : c == 1 ? s1 : s2, ostride = c == 1 ? s2 : s1;
+    uint8_t *dst0 = (uint8_t *)(c == 0 ? pl0 : c == 1 ? pl1 : pl2) + row_off(t.y0 + y0, stride) + (t.x0 + x0) * PXS;
+    uint8_t *dst1 = (joint & 1) ? (uint8_t *)(c == 1 ? pl2 : pl1) + row_off(t.y0 + y0, ostride) + (t.x0 + x0) * PXS : nullptr;
+    int *slot = (int *)f.coeffs + t.coeff_off;
+    // the samples the residual is added to are requested in front of the levels: one memory round trip on the critical path
+    uint2 p0[4], p1[4];
+#pragma unroll
+    for (int y = 0; y < 4; y++) {
+        p0[y] = p1[y] = make_uint2(0, 0);
+        if (!keep && y < rows && w >= 4) {
+            p0[y] = px4_load<BD>(dst0 + row_off(y, stride));
+            if (dst1)
+                p1[y] = px4_load<BD>(dst1 + row_off(y, ostride));
+        }
+    }
+
+    // levels: the lane's group of the packed stream (two 16-byte loads; a tile whose bit is clear loads nothing), or the int32 rows of its
+    // tile; nothing outside the nzw x nzh window is read
+    const int nzw = min((int)t.nzw, w), nzh = min((int)t.nzh, h);
+    int v[4][4];
+#pragma unroll
+    for (int y = 0; y < 4; y++)
+#pragma unroll
+        for (int x = 0; x < 4; x++)
+            v[y][x] = 0;
+    if (act && x0 < nzw && y0 < nzh) {
+        if (packed) {
+            if ((r.groups >> tile) & 1) {
+                const int16_t *g = (const int16_t *)f.levels + ((size_t)r.first + __popcll(r.groups & ((1ull << tile) - 1))) * 16;
+                const uint4 a = gld<uint4>(g), b = gld<uint4>(g + 8);
+                const int4 r0 = unpack_i16x4(make_uint2(a.x, a.y)), r1 = unpack_i16x4(make_uint2(a.z, a.w));
+                const int4 r2 = unpack_i16x4(make_uint2(b.x, b.y)), r3 = unpack_i16x4(make_uint2(b.z, b.w));
+                v[0][0] = r0.x; v[0][1] = r0.y; v[0][2] = r0.z; v[0][3] = r0.w;
+                v[1][0] = r1.x; v[1][1] = r1.y; v[1][2] = r1.z; v[1][3] = r1.w;
+                v[2][0] = r2.x; v[2][1] = r2.y; v[2][2] = r2.z; v[2][3] = r2.w;
+                v[3][0] = r3.x; v[3][1] = r3.y; v[3][2] = r3.z; v[3][3] = r3.w;
+            }
+        } else {
+#pragma unroll
+            for (int y = 0; y < 4; y++)
+                if (y < rows && y0 + y < nzh) {
+                    if (w >= 4) {
+                        const int4 q = gld<int4>(slot + ((y0 + y) << lw) + x0);
+                        v[y][0] = q.x; v[y][1] = q.y; v[y][2] = q.z; v[y][3] = q.w;
+                    } else {
+                        const int2 q = gld<int2>(slot + (y0 + y) * 2);
+                        v[y][0] = q.x; v[y][1] = q.y;
+                    }
+                }
+        }
+#pragma unroll
+        for (int y = 0; y < 4; y++)
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+                if (x0 + x >= nzw || y0 + y >= nzh)
+                    v[y][x] = 0;
+    }
+
+    if (t.flags & VVC355_TS_TU_BDPCM) {
+        const bool vert = t.flags & VVC355_TS_TU_VERTICAL;
+        if (vert)
+            ts_transpose(v);
+        ts_bdpcm_lines<MAXP>(v, vert ? gy : gx, vert ? tw : 1, f.range);
+        if (vert)
+            ts_transpose(v);
+    }
+
+    // the scaling process with ts = 1 (bd_shift 10, flat matrix): Dequant::apply's arithmetic, wrap included — after BDPCM a value can be
+    // -2^(range - 1) with range 20, outside the domain of apply_small
+    Dequant dq;
+    dq.setup(1, lw, lh, t.qp, 1, 0, BD, f.range, nullptr, 1, -1);
+#pragma unroll
+    for (int y = 0; y < 4; y++)
+#pragma unroll
+        for (int x = 0; x < 4; x++)
+            v[y][x] = dq.apply(v[y][x], 0, 0);
+
+#pragma unroll
+    for (int y = 0; y < 4; y++) {
+        if (y >= rows)
+            continue;
+        if (keep) {                                  // the whole w x h residual: BDPCM fills the block beyond the level window
+            if (w >= 4)
+                gst<int4>(slot + ((y0 + y) << lw) + x0, make_int4(v[y][0], v[y][1], v[y][2], v[y][3]));
+            else
+                gst<int2>(slot + (y0 + y) * 2, make_int2(v[y][0], v[y][1]));
+            continue;
+        }
+        int own[4], other[4];
+#pragma unroll
+        for (int x = 0; x < 4; x++) {
+            own[x] = resid_sample<BD>(v[y][x], joint & 8, scale);
+            other[x] = resid_sample<BD>(v[y][x], joint, scale);
+        }
+        uint8_t *row0 = dst0 + row_off(y, stride), *row1 = dst1 + row_off(y, ostride);
+        if (w >= 4) {
+            px4_add_store<BD>(row0, p0[y], own);
+            if (dst1)
+                px4_add_store<BD>(row1, p1[y], other);
+        } else {
+#pragma unroll
+            for (int x = 0; x < 2; x++) {
+                st_px<BD>(row0, x, clip_px<BD>(ld_px<BD>(row0, x) + own[x]));
+                if (dst1)
+                    st_px<BD>(row1, x, clip_px<BD>(ld_px<BD>(row1, x) + other[x]));
+            }
+        }
+    }
+}
+
+template <int BD>
+__global__ __launch_bounds__(256) void ts_tb_kernel(const vvc355_ts_tb_frame *__restrict__ fp, TsTbGrid g, int ch)
+{
+    const TsTbHead f = load_uniform((const TsTbHead *)fp);
+    const int b = blockIdx.x;
+    if (b < g.wg_first[0])
+        ts_tb_group<BD, 2, 4>(f, g.first[0], g.first[1], b, ch);
+    else if (b < g.wg_first[1])
+        ts_tb_group<BD, 8, 6>(f, g.first[1], g.first[2], b - g.wg_first[0], ch);
+    else if (b < g.wg_first[2])
+        ts_tb_group<BD, 16, 8>(f, g.first[2], g.first[3], b - g.wg_first[1], ch);
+    else if (b < g.wg_first[3])
+        ts_tb_group<BD, 64, 10>(f, g.first[3], g.first[4], b - g.wg_first[2], ch);
+}
+
+// one launch per requested channel type, its four classes in one grid
+template <int BD>
+static void launch_ts_tb(hipStream_t st, const vvc355_ts_tb_frame *fd, const vvc355_ts_tb_frame &fh, int channels)
+{
+    static const int kLanes[4] = { 2, 8, 16, 64 };
+    for (int ch = 0; ch < 2; ch++) {
+        if (!(channels & (1 << ch)))
+            continue;
+        TsTbGrid g;
+        int total = 0;
+        for (int k = 0; k < 4; k++) {
+            const int cnt = fh.class_first[ch][k + 1] - fh.class_first[ch][k], tbs = 256 / kLanes[k];
+            g.wg_first[k] = total += (cnt + tbs - 1) / tbs;
+        }
+        for (int k = 0; k < 5; k++)
+            g.first[k] = fh.class_first[ch][k];
+        if (total)
+            hipLaunchKernelGGL((ts_tb_kernel<BD>), dim3(total), dim3(256), 0, st, fd, g, ch);
+    }
+}
+
 } // namespace vvc355
 
 using namespace vvc355;
@@ -1281,6 +1554,37 @@ int vvc355_inter_tb_pass(void *stream, const vvc355_inter_tb_frame *frame_dev, c
     if (f->n_tus == 0)
         return 0;
     VVC355_BD_DISPATCH(f->bd, launch_inter_tb<BD>((hipStream_t)stream, frame_dev, *f, channels));
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int vvc355_ts_tb_pass(void *stream, const vvc355_ts_tb_frame *frame_dev, const vvc355_ts_tb_frame *frame_host, int channels)
+{
+    // the host copy is checked before any HIP call: a refused frame launches nothing
+    const vvc355_ts_tb_frame *f = frame_host;
+    if (!f || f->n_tus < 0 || f->class_first[0][0] != 0 || f->class_first[0][4] != f->class_first[1][0] || f->class_first[1][4] != f->n_tus)
+        return VVC355_TS_TB_E_CLASS;
+    for (int ch = 0; ch < 2; ch++)
+        for (int k = 0; k < 4; k++)
+            if (f->class_first[ch][k] > f->class_first[ch][k + 1])
+                return VVC355_TS_TB_E_CLASS;
+    if (f->bd != 8 && f->bd != 10 && f->bd != 12)
+        return VVC355_TS_TB_E_BD;
+    if (f->range < 15 || f->range > 20)
+        return VVC355_TS_TB_E_RANGE;
+    if (!f->lv != !f->levels)
+        return VVC355_TS_TB_E_LEVELS;
+    if (f->scale_table && f->size_y != 32 && f->size_y != 64)
+        return VVC355_TS_TB_E_SIZE_Y;
+    if (f->hs > 1 || f->vs > 1)
+        return VVC355_TS_TB_E_SHIFT;
+    if (channels < 1 || channels > 3)
+        return VVC355_TS_TB_E_CHANNELS;
+    if (channels == 3 && f->scale_table)
+        return VVC355_TS_TB_E_ORDER;
+    if (f->n_tus == 0)
+        return 0;
+    VVC355_BD_DISPATCH(f->bd, launch_ts_tb<BD>((hipStream_t)stream, frame_dev, *f, channels));
     HIP_CHECK(hipGetLastError());
     return 0;
 }

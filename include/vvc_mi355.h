@@ -372,8 +372,8 @@ int  vvc355_levels_pack(const int32_t *coeffs, int log2_w, int log2_h, int16_t *
  * uploaded and no job-build launch precedes it: the kernel makes its vvc355_itx_job in registers (flat scaling matrix, fused scaling
  * process, the transform types derived from the record's own tu_flags / mts_idx / lfnst_idx / c_idx), reads the levels from the packed
  * stream (or int32 in place), does LFNST on the staged block and leaves the residual in the arena slot at coeff_off, where the in-order
- * RECON pass adds it.  Transform skip, BDPCM, joint Cb-Cr and scaling lists are NOT covered: such blocks stay with vvc355_dequant_batch
- * and the BDPCM / residual entries.
+ * RECON pass adds it.  Transform skip, BDPCM, joint Cb-Cr and scaling lists are NOT covered: transform-skip and BDPCM blocks go to
+ * vvc355_ts_tb_pass, the others stay with vvc355_dequant_batch and the residual entries.
  *
  * Record order: the records are GROUPED BY AREA CLASS (log2_w + log2_h <= 4, 6, 8, 10, 12 -> class 0..4), class_first[k] .. class_first[k + 1]
  * being class k.  Grouping is the host's job, as shape grouping is for vvc355_itx_frame_build: a parser appends to five lists and
@@ -423,7 +423,8 @@ int vvc355_intra_tb_pass(void *stream, const vvc355_intra_tb_frame *frame_dev, c
  * (lmcs_scale_chroma :468-469, add_residual :472, add_residual_for_joint_coding_chroma :166-186) in one kernel per block.  No job array
  * (vvc355_itx_job, vvc355_lmcs_resid_job) is built and the scaled chroma residual never visits the arena: the kernel makes its job in
  * registers and adds the residual, scaled when asked, from the registers the transform left it in.  Transform skip, BDPCM and scaling
- * lists are NOT covered: such blocks stay with vvc355_dequant_batch and the residual entries.
+ * lists are NOT covered: transform-skip and BDPCM blocks go to vvc355_ts_tb_pass, blocks with scaling lists stay with
+ * vvc355_dequant_batch and the residual entries.
  *
  *   coeff_off   the block's slot in the arena, int32 elements, a multiple of 4: its int32 levels when the block is not packed, and its
  *               residual OUTPUT when KEEP is set; unused (and unchecked) otherwise
@@ -485,6 +486,74 @@ enum { VVC355_INTER_TB_E_BINS = -1, VVC355_INTER_TB_E_BD = -2, VVC355_INTER_TB_E
  * The host copy of the frame is checked before any HIP call.
  * returns 0, or a negative VVC355_INTER_TB_E_* with NOTHING launched */
 int vvc355_inter_tb_pass(void *stream, const vvc355_inter_tb_frame *frame_dev, const vvc355_inter_tb_frame *frame_host, int channels);
+
+/*
+ * The transform-skip blocks of a picture, BDPCM included, of intra and inter coding units alike, from one 16-byte record per coded block:
+ * what itransform does when tb->ts is set (vvc_intra.c:455-475), in its order — transform_bdpcm on the LEVELS (the clipped running sum
+ * along rows or columns, vvcdsp_template.c:76, :455-457), the scaling process with ts = 1 (bd_shift 10, no rectangular correction, no
+ * dep-quant add-in, flat matrix), no transform, the tail (add_residual :472, lmcs_scale_chroma :468-469,
+ * add_residual_for_joint_coding_chroma :166-186, or KEEP) — in one kernel, a lane per 4x4 tile, with no job array and no build launch.
+ * Blocks have sides 2..32 and at least 8 coefficients (transform skip is not coded above 32, and neither ISP nor SBT blocks use it).
+ *
+ *   coeff_off   the block's slot in the arena, int32 elements, a multiple of 4: its int32 levels when the block is not packed, and its
+ *               residual OUTPUT when KEEP is set; unused (and unchecked) otherwise
+ *   x0, y0      position in the component's samples
+ *   nzw, nzh    the window of the levels as residual coding left them (max_scan_x + 1, max_scan_y + 1, clamped to the block): levels
+ *               outside it are not read and count as 0
+ *   qp          tb->qp as derive_qp leaves it for a transform-skip block (the clip to qp_prime_ts_min is the host's job)
+ *   flags       bits 0-1 c_idx; bit 2 BDPCM; bit 3 KEEP: the WHOLE w x h residual goes to the arena slot (after BDPCM it reaches beyond
+ *               the level window) and the picture is not touched; bits 4 / 5 as in vvc355_inter_tu (the block's 64x64 unit minus the unit
+ *               of its coding unit's origin, per axis; read with joint bit 3 only); bit 6 BDPCM direction, 1 = vertical (read with bit 2
+ *               only); bit 7 reserved, 0
+ *   joint       bits 0-3 with the meaning of vvc355_recon_cmd.joint (joint flag, negative sign, shift, chroma residual scaling); bits 4-7
+ *               reserved, 0.  A joint transform unit is ONE record, as in vvc355_inter_tu: the second add goes to plane 3 - c_idx.
+ * Levels are int32 and accumulate in int32 as in the reference; a conforming level lies within the transform range.
+ *
+ * Record order: luma records first, then chroma, and inside a channel type GROUPED BY AREA CLASS (log2_w + log2_h <= 4, 6, 8, 10 -> class
+ * 0..3): records [class_first[ch][k], class_first[ch][k + 1]) are class k of channel type ch, so class_first[0][0] = 0, class_first[0][4] =
+ * class_first[1][0] and class_first[1][4] = n_tus.  Grouping is the host's job.  A block may be filed under a LARGER class than its area
+ * needs (slower, still correct).  lv[i] belongs to tus[i]; a packed picture may hold blocks with VVC355_LEVELS_INT32.
+ *
+ * A record that breaks the contract is SKIPPED, nothing is read or written for it: a side outside 2..32, fewer than 8 coefficients, an
+ * area larger than its class holds, reserved bits (the pad byte included), c_idx 3, c_idx 0 with joint bits, c_idx of the other channel
+ * type, joint bit 3 with scale_table == 0 or a unit left of / above the picture, a rectangle not inside its plane (for a joint record:
+ * either plane), coeff_off not a multiple of 4 where it is used.
+ */
+typedef struct vvc355_ts_tu {
+    uint32_t coeff_off;
+    int16_t  x0, y0;
+    uint8_t  log2_w, log2_h, nzw, nzh;
+    uint8_t  qp, pad_, flags, joint;       /* qp, flags and joint sit where vvc355_inter_tu has qp, flags and joint_mts */
+} vvc355_ts_tu;
+enum { VVC355_TS_TU_BDPCM = 4, VVC355_TS_TU_KEEP = 8, VVC355_TS_TU_UNIT_DX = 16, VVC355_TS_TU_UNIT_DY = 32, VVC355_TS_TU_VERTICAL = 64 };
+enum { VVC355_TS_TB_CLASSES = 4 };
+
+typedef struct vvc355_ts_tb_frame {
+    uint64_t tus;              /* DEVICE vvc355_ts_tu[n_tus], ordered as class_first says */
+    uint64_t coeffs;           /* DEVICE int32 arena: levels of unpacked blocks, residuals of KEEP blocks */
+    uint64_t lv, levels;       /* DEVICE vvc355_tb_levels[n_tus] paired by index + the int16 group stream; both 0 = int32 levels in place at coeff_off */
+    uint64_t plane[3];         /* DEVICE: sample (0, 0) of each component */
+    uint64_t scale_table;      /* DEVICE int16: vvc355_lmcs_scale_frame.scale as vvc355_lmcs_vpdu_scale_pass left it; 0 = no record may set joint bit 3 */
+    int32_t  stride[3];        /* bytes */
+    int32_t  width, height;    /* luma picture size */
+    int32_t  n_tus;
+    uint8_t  hs, vs;           /* chroma shifts, 0 or 1 */
+    uint8_t  size_y;           /* min(CtbSizeY, 64): 32 or 64; read with scale_table only */
+    uint8_t  range, bd;        /* log2_transform_range 15..20; bit depth 8 / 10 / 12 */
+    uint8_t  pad_[3];
+    int32_t  class_first[2][VVC355_TS_TB_CLASSES + 1];
+} vvc355_ts_tb_frame;
+
+/* what vvc355_ts_tb_pass returns for a frame it refuses: class_first not non-decreasing from 0 to n_tus through both channel types (or
+ * n_tus < 0, or no frame); bd not 8 / 10 / 12; range outside 15..20; only one of lv / levels set; size_y not 32 / 64 with a scale table;
+ * hs or vs above 1; channels outside 1..3; channels == 3 with a scale table (the table is made from the luma this stage reconstructs) */
+enum { VVC355_TS_TB_E_CLASS = -1, VVC355_TS_TB_E_BD = -2, VVC355_TS_TB_E_RANGE = -3, VVC355_TS_TB_E_LEVELS = -4,
+       VVC355_TS_TB_E_SIZE_Y = -5, VVC355_TS_TB_E_SHIFT = -6, VVC355_TS_TB_E_CHANNELS = -7, VVC355_TS_TB_E_ORDER = -8 };
+/* Runs the stage on `stream` for the channel types in `channels` (1 luma, 2 chroma, 3 both): one launch per channel type, its four
+ * classes in one grid.  A picture with chroma residual scaling calls it (and vvc355_inter_tb_pass, in either order: the two own disjoint
+ * blocks) with 1, then vvc355_lmcs_vpdu_scale_pass, then with 2.  The host copy of the frame is checked before any HIP call.
+ * returns 0, or a negative VVC355_TS_TB_E_* with NOTHING launched */
+int vvc355_ts_tb_pass(void *stream, const vvc355_ts_tb_frame *frame_dev, const vvc355_ts_tb_frame *frame_host, int channels);
 
 /*
  * Scaling process for transform coefficients (dequant) — NOT a table slot in the reference: host C in
