@@ -5,12 +5,18 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may link or call it, and only as the
  * checker / CPU baseline — never as a fallback for the HIP path.
  *
- * PARITY UNPINNED: the reference's own tests hold no golden vectors for this path (checkasm
- * compares the C template with an override at run time; the FATE framecrc lists need bitstreams
- * that are not in the container), and the reference's C path cannot be compiled here without its
- * configure-generated headers (config.h, libavutil/avconfig.h).  Every function below therefore
- * restates the reference algorithm from a reading of the cited file:line, and is cross-checked
- * only by independent properties (tests/test_oracle_*.py).
+ * Every function restates the reference algorithm from a reading of the cited file:line.
+ * PINNED bit-exactly against the reference's own C path (ref_shim.c, `make ref`): the leaf slots of
+ * VVCDSPContext and the non-static helpers, on the case lists of tests/ref_cases.py (digests in
+ * tests/golden/ref_slots.json) and, where the reference is present, on a wider sweep
+ * (tests/test_oracle_ref_cpu.py).
+ * STILL UNPINNED, cross-checked only by independent properties (tests/test_oracle_cpu.py):
+ * the three slots that take a populated VVCLocalContext (intra.intra_pred, intra.intra_cclm_pred,
+ * intra.lmcs_scale_chroma: orc_intra_pred_flat, orc_intra_cclm_pred_flat, orc_lmcs_chroma_scale_flat
+ * / orc_lmcs_scale_chroma_flat), the static functions of vvc_intra.c (dequant,
+ * derive_transform_type, ilfnst_transform: orc_dequant, orc_derive_transform_type,
+ * orc_ilfnst_transform) and the caller restatements (orc_bipred_block, orc_gpm_block,
+ * orc_affine_block, orc_lmcs_chroma_resid_block, every orc_*_pass and orc_*_frame_build).
  *
  * Conventions: `bd` = bit depth (8, 10 or 12); pixels are uint8_t when bd == 8 and uint16_t
  * otherwise; pixel strides are in BYTES exactly as on the reference's function-pointer surface

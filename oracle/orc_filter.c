@@ -1,6 +1,6 @@
 /*
  * oracle/orc_filter.c — CPU restatement of the in-loop filter DSP slots (LMCS, ALF, SAO, deblock).
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see orc_common.h).
+ * TEST INFRASTRUCTURE ONLY; slots PINNED, frame passes UNPINNED (see orc_common.h).
  *
  * Follows, by reading:
  *   libavcodec/vvc/vvc_filter_template.c   (lmcs :25, alf :38-408, deblock :466-804)

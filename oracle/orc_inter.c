@@ -1,6 +1,6 @@
 /*
  * oracle/orc_inter.c — CPU restatement of the inter-prediction DSP slots.
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see orc_common.h).
+ * TEST INFRASTRUCTURE ONLY; slots PINNED, block / frame callers UNPINNED (see orc_common.h).
  *
  * Follows, by reading:
  *   libavcodec/h26x/h2656_inter_template.c  (put/put_uni/put_uni_w x {pixels,h,v,hv}, luma :29-334, chroma :336-577)

@@ -1,6 +1,6 @@
 /*
  * oracle/orc_intra.c — CPU restatement of the intra-prediction DSP slots.
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see orc_common.h).
+ * TEST INFRASTRUCTURE ONLY; leaf predictors and mode helpers PINNED, the flattened context-taking slots UNPINNED (see orc_common.h).
  *
  * Follows, by reading:
  *   libavcodec/vvc/vvc_intra_template.c  (ref_filter :450, prepare_intra_edge_params :467, intra_pred :595, planar :686,
@@ -65,6 +65,13 @@ static int ref_filter_mode(int mode)                /* :655 */
         if (modes[i] == mode)
             return 1;
     return 0;
+}
+
+ORC_API int orc_intra_ref_filter_flag(int mode) { return ref_filter_mode(mode); }
+
+ORC_API int orc_intra_mip_size_id(int w, int h)     /* :529 */
+{
+    return (w == 4 && h == 4) ? 0 : ((w == 4 || h == 4) || (w == 8 && h == 8)) ? 1 : 2;
 }
 
 /* ------------------------------------------------------------------ leaf predictors */
@@ -205,7 +212,7 @@ ORC_API void orc_pred_mip(int bd, uint8_t *src, const uint8_t *top, const uint8_
     int mode_id, int is_transposed)
 {
     const int wide = bd > 8;
-    const int size_id = (w == 4 && h == 4) ? 0 : ((w == 4 || h == 4) || (w == 8 && h == 8)) ? 1 : 2;
+    const int size_id = orc_intra_mip_size_id(w, h);
     const int bsize = size_id == 0 ? 2 : 4, psize = size_id == 2 ? 8 : 4;
     const int in_size = 2 * bsize - (size_id == 2);
     const uint8_t *matrix = size_id == 0 ? orc_tab_mip_matrix_4x4 + mode_id * 16 * 4

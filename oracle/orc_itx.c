@@ -1,6 +1,6 @@
 /*
  * oracle/orc_itx.c — CPU restatement of the inverse-transform / residual DSP slots.
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see orc_common.h).
+ * TEST INFRASTRUCTURE ONLY; slots and 1-D kernels PINNED, orc_dequant UNPINNED (see orc_common.h).
  *
  * Follows, by reading:
  *   libavcodec/vvc/vvc_itx_1d.c   (DCT-2 butterflies :88-653 and their nz gating :64-67, matrix_mul :657, LFNST :708)
@@ -32,11 +32,13 @@ static int dct2_input_used(int n, int k, size_t nz)
     return k < 2 || nz > (size_t)pow2_floor(k);
 }
 
-ORC_API void orc_inv_tx_1d(int type, int n, int *c, ptrdiff_t stride, size_t nz)
+ORC_API int orc_inv_tx_1d(int type, int n, int *c, ptrdiff_t stride, size_t nz)
 {
     int in[64], out[64];
+    if (type < ORC_DCT2 || type > ORC_DCT8 || n < 1 || n > 64 || (n & (n - 1)) || (type != ORC_DCT2 && (n == 2 || n == 64)))
+        return -1;                                /* no such kernel: DCT-2 has 1..64, DST-7 / DCT-8 have 1 and 4..32 */
     if (n == 1)
-        return;                                   /* the *_1 stubs, vvc_itx_1d.c:70-80 */
+        return 0;                                 /* the *_1 stubs, vvc_itx_1d.c:70-80 */
     if (type == ORC_DCT2) {
         const int step = 64 / n;
         for (int k = 0; k < n; k++)
@@ -64,6 +66,7 @@ ORC_API void orc_inv_tx_1d(int type, int n, int *c, ptrdiff_t stride, size_t nz)
     }
     for (int i = 0; i < n; i++)
         c[i * stride] = out[i];
+    return 0;
 }
 
 /* which (trh, trv, log2 w, log2 h) the reference installs, vvcdsp_template.c:142-159 */

@@ -1,6 +1,6 @@
 /*
  * oracle/orc_recon.c — the RECON stage of a picture as the decoder runs it per CTU, and the two transform-side helpers that sit
- * between dequant and the inverse transform (TEST INFRASTRUCTURE ONLY; PARITY UNPINNED, see orc_common.h).
+ * between dequant and the inverse transform (TEST INFRASTRUCTURE ONLY; UNPINNED, see orc_common.h).
  *
  *  - ilfnst_transform          libavcodec/vvc/vvc_intra.c:65-127
  *  - derive_transform_type     libavcodec/vvc/vvc_intra.c:130-164
@@ -193,6 +193,11 @@ static int wide_angle_mode_mapping(int isp_split, int c_idx, int tb_width, int t
     else if (nh > nw && mode <= 66 && mode > min)
         mode -= 67;
     return mode;
+}
+
+ORC_API int orc_intra_wide_angle(int isp_split, int c_idx, int tb_width, int tb_height, int cb_width, int cb_height, int mode)
+{
+    return wide_angle_mode_mapping(isp_split, c_idx, tb_width, tb_height, cb_width, cb_height, mode);
 }
 
 /* when set, the pass stops at command `dbg_k` of CTU `dbg_rs` (a PRED) and reports the flattened job instead of predicting */

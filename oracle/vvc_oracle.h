@@ -1,6 +1,6 @@
 /*
- * oracle/vvc_oracle.h — C API of the CPU oracle (TEST INFRASTRUCTURE ONLY; PARITY UNPINNED,
- * see orc_common.h).  One function per slot of the reference's VVCDSPContext
+ * oracle/vvc_oracle.h — C API of the CPU oracle (TEST INFRASTRUCTURE ONLY; leaf slots and helpers
+ * pinned against the reference, callers and context-taking slots unpinned: see orc_common.h).  One function per slot of the reference's VVCDSPContext
  * (libavcodec/vvc/vvcdsp.h:48-168): same argument order and meaning, with the bit depth the
  * reference selects at ff_vvc_dsp_init() time (vvcdsp.c:228) passed as a leading `bd` argument,
  * and table indices (luma/chroma, frac/int, h/v) passed as leading ints.
@@ -82,8 +82,9 @@ void orc_dmvr(int bd, int vfrac, int hfrac, int16_t *dst, const uint8_t *src, pt
 
 /* ---- inverse transform + residual (orc_itx.c) ---- */
 enum { ORC_DCT2 = 0, ORC_DST7 = 1, ORC_DCT8 = 2 };
-/* 1-D kernels on a strided int vector; n = 1,2,4,..,64 (DCT2) or 1,4,8,16,32 (DST7/DCT8) */
-void orc_inv_tx_1d(int type, int n, int *coeffs, ptrdiff_t stride, size_t nz);
+/* 1-D kernels on a strided int vector; n = 1,2,4,..,64 (DCT2) or 1,4,8,16,32 (DST7/DCT8); returns 0, or -1 (vector untouched)
+ * where there is no kernel of that type and size */
+int  orc_inv_tx_1d(int type, int n, int *coeffs, ptrdiff_t stride, size_t nz);
 /* itx.itx[trh][trv][log2 w][log2 h]; returns 0, or -1 when the reference table has no entry for that combination */
 void orc_dequant(int *coeffs, int log2_w, int log2_h, int min_x, int min_y, int max_x, int max_y, int qp, int ts,
                  int dep_quant, int bit_depth, int log2_transform_range, const uint8_t *scale_matrix,
@@ -312,6 +313,9 @@ int  orc_intra_pred_angle(int mode);
 int  orc_intra_inv_angle(int angle);
 int  orc_intra_nscale(int w, int h, int mode);
 int  orc_intra_need_pdpc(int w, int h, int bdpcm_flag, int mode, int ref_idx);
+int  orc_intra_ref_filter_flag(int mode);
+int  orc_intra_mip_size_id(int w, int h);
+int  orc_intra_wide_angle(int isp_split, int c_idx, int tb_width, int tb_height, int cb_width, int cb_height, int mode);
 void orc_pred_planar(int bd, uint8_t *src, const uint8_t *top, const uint8_t *left, int w, int h, ptrdiff_t stride);
 void orc_pred_dc(int bd, uint8_t *src, const uint8_t *top, const uint8_t *left, int w, int h, ptrdiff_t stride);
 void orc_pred_v(int bd, uint8_t *src, const uint8_t *top, int w, int h, ptrdiff_t stride);

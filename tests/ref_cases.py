@@ -1,0 +1,994 @@
+"""Deterministic case lists for the leaf slots of the DSP surface and the mode / transform helpers.
+
+One list per slot, shared by tests/test_oracle_ref_cpu.py (oracle vs the live reference), tools/gen_golden.py (digests of
+the reference's outputs, tests/golden/ref_slots.json), tests/test_golden_cpu.py (oracle vs digests) and tests/test_golden_gpu.py
+(HIP vs digests).  Every case is the literal argument list of orc_<slot> / ref_<slot> / vvc355_<slot>: ints and `Buf`s.
+
+Inputs come from `Gen`, a counter-based splitmix64 written here on uint64 arrays, so two numpy versions cannot disagree.
+`cases(slot)` is the committed list (seed 0).  `cases(slot, seed=k)`, k > 0, is one round of the wide sweep of the live-reference
+test: it keeps the list's table indices and redraws everything else, so that no case repeats one of the list or of another
+round: the free block shapes (`shapes`), filters, fractions, heights, weights, and every sample, the fixed patterns included
+(`field` mixes the extremes with random samples there).  The helpers in `EXHAUSTIVE` list their whole domain and have no sweep.
+
+Distributions (`DISTS`): uniform random, all-minimum, all-maximum, and a checkerboard of the two extremes.  For int16
+prediction intermediates the extremes are what `put` can emit at that bit depth (`put_range`), for DMVR planes what `dmvr`
+can emit (`dmvr_max`).  Destinations are pre-filled with a sentinel and compared whole.
+
+Each builder states its input domain in one line; everything stays inside what the decoder can produce, because the oracle
+is built with -fwrapv and the reference is not: outside the domain a difference is not a finding.
+"""
+import ctypes
+import os
+import zlib
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PB = 128                                  # MAX_PB_SIZE: implicit row stride of int16 intermediates
+SAO_SS_BYTES = 2 * 128 + 64               # ORC_SAO_EDGE_SRC_STRIDE
+DISTS = ("uniform", "min", "max", "checker")
+BDS = (8, 10, 12)
+S16, SPX = 0x1234, 0x55                   # sentinels of int16 / pixel destinations
+GROUP = 64                                # cases per digest group
+
+_GAMMA, _M1, _M2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
+
+
+class Gen:
+    """splitmix64 in counter mode: value i of stream `seed` is mix(seed + (i + 1) * gamma)."""
+
+    def __init__(self, name, seed=0):
+        self.base = np.uint64(zlib.crc32(name.encode()) | (seed << 32))
+        self.ctr, self.seed = 0, seed
+
+    def u64(self, n):
+        with np.errstate(over="ignore"):
+            z = self.base + np.arange(self.ctr + 1, self.ctr + n + 1, dtype=np.uint64) * _GAMMA
+            self.ctr += n
+            z = (z ^ (z >> np.uint64(30))) * _M1
+            z = (z ^ (z >> np.uint64(27))) * _M2
+            return z ^ (z >> np.uint64(31))
+
+    def ints(self, lo, hi, shape=None):
+        """Integers in [lo, hi) as int64 (a scalar int when shape is None)."""
+        n = 1 if shape is None else int(np.prod(shape))
+        v = (self.u64(n) % np.uint64(hi - lo)).astype(np.int64) + lo
+        return int(v[0]) if shape is None else v.reshape(shape)
+
+    def pick(self, seq):
+        return seq[self.ints(0, len(seq))]
+
+
+class Buf:
+    """A pointer argument: `arr` is copied per run, the callee gets the address of element `off`.  `scratch` buffers are
+    work areas whose contents after the call are not part of the slot's result."""
+
+    def __init__(self, arr, off=0, scratch=False):
+        self.arr, self.off, self.scratch = np.ascontiguousarray(arr), int(off), scratch
+
+
+class Case:
+    def __init__(self, slot, key, params, args, ret=False):
+        self.slot, self.key, self.params, self.args, self.ret = slot, key, params, args, ret
+
+
+def px_dtype(bd):
+    return np.uint8 if bd == 8 else np.uint16
+
+
+def field(g, shape, lo, hi, dist, dtype):
+    """Samples in [lo, hi] (inclusive) of distribution `dist`.  In the sweep (seed > 0) the three fixed patterns become random mixes, a
+    quarter of the samples uniform and the rest mostly `lo`, mostly `hi`, or either: still the extremes, and never the same field twice."""
+    if dist == "uniform":
+        a = g.ints(lo, hi + 1, shape)
+    elif g.seed:
+        sel, rnd = g.ints(0, 8, shape), g.ints(lo, hi + 1, shape)
+        ext = {"min": np.where(sel == 2, hi, lo), "max": np.where(sel == 2, lo, hi), "checker": np.where(sel & 1, hi, lo)}[dist]
+        a = np.where(sel >= 6, rnd, ext)
+    elif dist == "min":
+        a = np.full(shape, lo, np.int64)
+    elif dist == "max":
+        a = np.full(shape, hi, np.int64)
+    else:
+        idx = np.indices(shape).sum(axis=0) & 1
+        a = np.where(idx, hi, lo).astype(np.int64)
+    return a.astype(dtype)
+
+
+def shapes(g, listed, ws, hs):
+    """The (w, h) of a builder: the listed ones, or in the sweep as many drawn from the sizes `ws` x `hs` the slot may be called with."""
+    if not g.seed:
+        return listed
+    return [(g.pick(ws), g.pick(hs)) for _ in listed]
+
+
+POW2 = [2, 4, 8, 16, 32, 64, 128]
+MULT4 = list(range(4, 129, 4))
+
+
+def pixels(g, shape, bd, dist):
+    return field(g, shape, 0, (1 << bd) - 1, dist, px_dtype(bd))
+
+
+_tabs = None
+
+
+def filter_tables():
+    """(luma [3][16][8], chroma [3][32][4]) interpolation filters, from the oracle's copy of the constant tables (pinned by
+    tests/golden/tables_sha256.json)."""
+    global _tabs
+    if _tabs is None:
+        lib = ctypes.CDLL(os.path.join(ROOT, "oracle", "liborc.so"))
+        luma = np.ctypeslib.as_array((ctypes.c_int8 * 384).in_dll(lib, "orc_tab_inter_luma_filters")).reshape(3, 16, 8).copy()
+        chroma = np.ctypeslib.as_array((ctypes.c_int8 * 384).in_dll(lib, "orc_tab_inter_chroma_filters")).reshape(3, 32, 4).copy()
+        _tabs = (luma, chroma)
+    return _tabs
+
+
+_put_range = {}
+
+
+def put_range(bd):
+    """[lo, hi] of what inter.put can store at `bd`: integer position px << (14 - bd); one pass sum(tap * px) >> (bd - 8);
+    two passes sum(tap * first) >> 6 with the first pass at its own extremes; the store is int16, so the bound is cut there."""
+    if bd not in _put_range:
+        mx = (1 << bd) - 1
+        lo, hi = 0, mx << (14 - bd)
+        for tab in filter_tables():
+            f = tab.reshape(-1, tab.shape[-1]).astype(np.int64)
+            pos, neg = np.where(f > 0, f, 0).sum(axis=1), np.where(f < 0, f, 0).sum(axis=1)
+            h_hi, h_lo = int(pos.max() * mx) >> (bd - 8), int(neg.min() * mx) >> (bd - 8)
+            hv_hi = int((pos * h_hi + neg * h_lo).max()) >> 6
+            hv_lo = int((pos * h_lo + neg * h_hi).min()) >> 6
+            lo, hi = min(lo, h_lo, hv_lo), max(hi, h_hi, hv_hi)
+        _put_range[bd] = (max(lo, -32768), min(hi, 32767))
+    return _put_range[bd]
+
+
+def inter16(g, shape, bd, dist):
+    lo, hi = put_range(bd)
+    return field(g, shape, lo, hi, dist, np.int16)
+
+
+def dmvr_max(bd):
+    """Largest sample inter.dmvr can store: px << (10 - bd) up to 10 bit, (px + half) >> (bd - 10) above; the bilinear taps sum to 16."""
+    mx = (1 << bd) - 1
+    return mx << (10 - bd) if bd <= 10 else (mx + (1 << (bd - 11))) >> (bd - 10)
+
+
+def dist_cycle(i):          # callers pass len(out) (+ g.seed)
+    """Distribution of the i-th case of a long list: half uniform, a quarter checkerboard, an eighth each extreme."""
+    return ("uniform", "checker", "uniform", "min", "uniform", "checker", "uniform", "max")[i & 7]
+
+
+# ---------------------------------------------------------------------------------------------------------------- inter
+
+# weighted prediction, explicit (7.4.8.2 / pred_weight_table): luma_log2_weight_denom 0..7, weight = 2^denom + delta with
+# delta in [-128, 127] -> [-127, 255]; offsets in [-128, 127] (no high-precision offsets)
+WP_EXTREMES = [(0, -127, -128), (7, 255, 127), (7, -127, 127), (0, 255, -128), (3, 255, -128), (5, 1, 0)]
+
+
+def wp_params(g, i):
+    if i % 3 == 0:
+        return WP_EXTREMES[(i // 3) % len(WP_EXTREMES)]
+    return g.ints(0, 8), g.ints(-127, 256), g.ints(-128, 128)
+
+
+def _put_like(slot, g):
+    """Domain: pixels in [0, 2^bd), filters = rows of the two interpolation tables, heights 2..16, widths 2..128."""
+    luma_f, chroma_f = filter_tables()
+    out, i = [], 0
+    for bd in BDS:
+        for chroma in (0, 1):
+            widths = ([2, 4, 8, 12, 16, 24, 32, 48, 64, 96, 128] if chroma else [4, 8, 12, 16, 24, 32, 48, 64, 96, 128])
+            for w in widths:
+                for vfrac in (0, 1):
+                    for hfrac in (0, 1):
+                        for dist in DISTS:
+                            h = g.pick([2, 4, 6, 8, 12, 16] if chroma else [4, 8, 12, 16])
+                            plane = pixels(g, (h + 16, w + 24), bd, dist)
+                            ps, W = plane.itemsize, plane.shape[1]
+                            tab, nph = (chroma_f, 32) if chroma else (luma_f, 16)
+                            fset = g.ints(0, 3)
+                            mx, my = (g.ints(1, nph) if hfrac else 0), (g.ints(1, nph) if vfrac else 0)
+                            hf, vf = Buf(tab[fset, mx]), Buf(tab[fset, my])
+                            src = Buf(plane, 8 * W + 8)
+                            denom, wx, ox = wp_params(g, i)
+                            i += 1
+                            prm = dict(bd=bd, chroma=chroma, w=w, h=h, vfrac=vfrac, hfrac=hfrac, fset=fset, mx=mx, my=my, dist=dist)
+                            key = (bd, chroma)
+                            if slot == "put":
+                                d = Buf(np.full((h + 2, PB), S16, np.int16), PB)
+                                args = [bd, chroma, vfrac, hfrac, d, src, W * ps, h, hf, vf, w]
+                            else:
+                                dw = w + 8
+                                d = Buf(np.full((h + 2, dw), SPX, plane.dtype), dw + 4)
+                                if slot == "put_uni":
+                                    args = [bd, chroma, vfrac, hfrac, d, dw * ps, src, W * ps, h, hf, vf, w]
+                                else:
+                                    prm.update(denom=denom, wx=wx, ox=ox)
+                                    args = [bd, chroma, vfrac, hfrac, d, dw * ps, src, W * ps, h, denom, wx, ox, hf, vf, w]
+                            out.append(Case(slot, key, prm, args))
+    return out
+
+
+BLEND_SHAPES = [(2, 2), (4, 4), (8, 16), (16, 4), (32, 8), (64, 2), (128, 16), (12, 6), (128, 3)]
+
+
+def _blend(slot, g):
+    """Domain: int16 sources in put_range(bd) at row stride 128; weights / offsets / denominators as the syntax bounds them."""
+    out, i = [], 0
+    for bd in BDS:
+        dt = px_dtype(bd)
+        ps = np.dtype(dt).itemsize
+        for (w, h) in shapes(g, BLEND_SHAPES, POW2 + [12, 24, 48, 96], range(2, 17)):
+            for dist in DISTS:
+                for rep in range(6 if slot == "w_avg" else 1):
+                    s0, s1 = Buf(inter16(g, (h, PB), bd, dist)), Buf(inter16(g, (h, PB), bd, "uniform" if dist == "uniform" else DISTS[1 + (DISTS.index(dist) + rep) % 3]))
+                    dw = w + 8
+                    d = Buf(np.full((h + 2, dw), SPX, dt), dw + 4)
+                    prm = dict(bd=bd, w=w, h=h, dist=dist)
+                    if slot == "avg":
+                        args = [bd, d, dw * ps, s0, s1, w, h]
+                    else:
+                        # bi-prediction: explicit weights as wp_params; BCW (7.4.12.7) weights {-2, 3, 4, 5, 10} / 8 with denom 2 + 1 and no offsets
+                        if rep == 5:
+                            w1 = g.pick([-2, 3, 4, 5, 10])
+                            denom, w0, o0, o1 = 2, 8 - w1, 0, 0
+                        else:
+                            denom, w0, o0 = wp_params(g, i)
+                            _, w1, o1 = wp_params(g, i + 1)
+                            i += 1
+                        prm.update(denom=denom, w0=w0, w1=w1, o0=o0, o1=o1)
+                        args = [bd, d, dw * ps, s0, s1, w, h, denom, w0, w1, o0, o1]
+                    out.append(Case(slot, (bd,), prm, args))
+    return out
+
+
+def _put_ciip(slot, g):
+    """Domain: pixels; intra weight 1..3 (8.5.6.7)."""
+    out = []
+    for bd in BDS:
+        for (w, h) in shapes(g, [(4, 4), (8, 16), (16, 4), (32, 8), (64, 2), (64, 16)], POW2[1:6], range(2, 17)):
+            for dist in DISTS:
+                for iw in (1, 2, 3):
+                    dw = w + 8
+                    dst = pixels(g, (h + 2, dw), bd, dist)
+                    inter = pixels(g, (h, dw), bd, "uniform" if dist == "uniform" else DISTS[1 + (DISTS.index(dist) + iw) % 3])
+                    ps = dst.itemsize
+                    out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, iw=iw, dist=dist),
+                                    [bd, Buf(dst, dw + 4), dw * ps, w, h, Buf(inter), dw * ps, iw]))
+    return out
+
+
+def _put_gpm(slot, g):
+    """Domain: int16 sources in put_range(bd); weights 0..8; the weight walk steps +-1 / +-2 per sample and +-pitch / +-2 pitch per
+    row (mirrored and flipped partitions, chroma at half resolution; ff_vvc_gpm_weights layout)."""
+    out = []
+    MW, MH = 288, 72
+    for bd in BDS:
+        dt = px_dtype(bd)
+        ps = np.dtype(dt).itemsize
+        for (w, h) in [(8, 8), (16, 8), (8, 16), (32, 16), (64, 8), (64, 16), (4, 4)]:
+            for (sx, sy) in [(1, MW), (-1, MW), (1, -MW), (-1, -MW), (2, 2 * MW), (-2, -2 * MW), (2, -2 * MW), (-2, 2 * MW)]:
+                for dist in DISTS:
+                    s0 = Buf(inter16(g, (h, PB), bd, dist))
+                    s1 = Buf(inter16(g, (h, PB), bd, "uniform" if dist == "uniform" else "checker"))
+                    mask = field(g, (MH, MW), 0, 8, dist, np.uint8)
+                    dw = w + 8
+                    d = Buf(np.full((h + 2, dw), SPX, dt), dw + 4)
+                    out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, step_x=sx, step_y=sy, dist=dist),
+                                    [bd, d, dw * ps, w, h, s0, s1, Buf(mask, (MH // 2) * MW + MW // 2), sx, sy]))
+    return out
+
+
+ORG16 = 4 * PB + 8          # origin of an int16 block inside its plane: leaves the ring the slots touch around the block
+
+
+def _fetch(slot, g):
+    """Domain: pixels; fractions 0..15.  The slot writes the one-sample ring around the w x h block at row stride 128."""
+    out = []
+    for bd in BDS:
+        shapes = [(8, 8), (16, 16), (16, 8), (8, 16)] if slot == "bdof_fetch_samples" else [(4, 4)]
+        for (w, h) in shapes:
+            for xf in (0, 7, 8, 15):
+                for yf in (0, 7, 8, 15):
+                    dist = dist_cycle(len(out))
+                    plane = pixels(g, (h + 16, w + 24), bd, dist)
+                    W, ps = plane.shape[1], plane.itemsize
+                    d = Buf(np.full((h + 8, PB), S16, np.int16), ORG16)
+                    args = [bd, d, Buf(plane, 8 * W + 8), W * ps, xf, yf] + ([w, h] if slot == "bdof_fetch_samples" else [])
+                    out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, xf=xf, yf=yf, dist=dist), args))
+    return out
+
+
+def _prof_grad(slot, g):
+    """Domain: int16 source in put_range(bd) with a one-sample ring; pad 0 (PROF) or 1 (BDOF)."""
+    out = []
+    for bd in BDS:
+        for (w, h) in [(4, 4), (8, 8), (16, 8), (8, 16), (16, 16)]:
+            for pad in (0, 1):
+                for dist in DISTS:
+                    src = Buf(inter16(g, (h + 8, PB), bd, dist), ORG16)
+                    gs = 24
+                    g0, g1 = Buf(np.full((h + 4, gs), 0x1111, np.int16)), Buf(np.full((h + 4, gs), 0x2222, np.int16))
+                    out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, pad=pad, dist=dist), [bd, g0, g1, gs, src, PB, w, h, pad]))
+    return out
+
+
+def _apply_prof(slot, g):
+    """Domain: int16 4x4 source in put_range(bd) with ring; diff_mv in [-32, 31] (dmvLimit 2^5, 8.5.5.9); weights as wp_params."""
+    out = []
+    for bd in BDS:
+        dt = px_dtype(bd)
+        ps = np.dtype(dt).itemsize
+        for dist in DISTS:
+            for mvd in DISTS:
+                for rep in range(6 if slot == "apply_prof_uni_w" else 2):
+                    src = Buf(inter16(g, (12, PB), bd, dist), ORG16)
+                    dx, dy = Buf(field(g, (16,), -32, 31, mvd, np.int16)), Buf(field(g, (16,), -32, 31, "uniform" if rep & 1 else mvd, np.int16))
+                    prm = dict(bd=bd, dist=dist, mv_dist=mvd, rep=rep)
+                    if slot == "apply_prof":
+                        args = [bd, Buf(np.full((6, PB), S16, np.int16), PB), src, dx, dy]
+                    else:
+                        d = Buf(np.full((6, 12), SPX, dt), 12 + 4)
+                        args = [bd, d, 12 * ps, src, dx, dy]
+                        if slot == "apply_prof_uni_w":
+                            denom, wx, ox = wp_params(g, len(out))
+                            prm.update(denom=denom, wx=wx, ox=ox)
+                            args += [denom, wx, ox]
+                    out.append(Case(slot, (bd,), prm, args))
+    return out
+
+
+def _apply_bdof(slot, g):
+    """Domain: two int16 blocks in put_range(bd) whose ring the slot itself pads (both sources are outputs too); 8 / 16 sizes."""
+    out = []
+    for bd in BDS:
+        dt = px_dtype(bd)
+        ps = np.dtype(dt).itemsize
+        for (w, h) in [(8, 8), (16, 16), (16, 8), (8, 16)]:
+            for dist in DISTS:
+                for d1 in ("same", "uniform", "checker"):
+                    a = inter16(g, (h + 8, PB), bd, dist)
+                    b = a.copy() if d1 == "same" else inter16(g, (h + 8, PB), bd, d1)
+                    if d1 == "same" and dist == "uniform":      # nearly equal predictions: the refinement is small but not zero
+                        b = np.clip(b.astype(np.int64) + g.ints(-64, 65, b.shape), *put_range(bd)).astype(np.int16)
+                    dw = w + 8
+                    d = Buf(np.full((h + 2, dw), SPX, dt), dw + 4)
+                    out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, dist=dist, other=d1), [bd, d, dw * ps, Buf(a, ORG16), Buf(b, ORG16), w, h]))
+    return out
+
+
+def _sad(slot, g):
+    """Domain: DMVR planes, samples in [0, dmvr_max]; search offsets dx, dy in 0..4 (+-2 around the centre)."""
+    out = []
+    hi = max(dmvr_max(bd) for bd in BDS)
+    for (w, h) in [(8, 8), (16, 16), (16, 8), (8, 16)]:
+        for dist in DISTS:
+            s0 = field(g, (h + 6, PB), 0, hi, dist, np.int16)
+            s1 = field(g, (h + 6, PB), 0, hi, "uniform" if dist == "uniform" else DISTS[1 + (DISTS.index(dist) + 1) % 3], np.int16)
+            for dx in range(5):
+                for dy in range(5):
+                    out.append(Case(slot, (0, w, h), dict(w=w, h=h, dx=dx, dy=dy, dist=dist), [Buf(s0), Buf(s1), dx, dy, w, h], ret=True))
+    return out
+
+
+def _dmvr(slot, g):
+    """Domain: pixels; 1/16 fractions 1..15 on the filtered axes; block = sub-block + 4 (12, 20) and the plain sizes."""
+    out = []
+    for bd in BDS:
+        for vfrac in (0, 1):
+            for hfrac in (0, 1):
+                for (w, h) in [(12, 12), (20, 20), (20, 12), (12, 20), (8, 8)]:
+                    for dist in DISTS:
+                        plane = pixels(g, (h + 16, w + 24), bd, dist)
+                        W, ps = plane.shape[1], plane.itemsize
+                        mx, my = g.pick([1, 8, 15, g.ints(1, 16)]), g.pick([1, 8, 15, g.ints(1, 16)])
+                        d = Buf(np.full((h + 2, PB), S16, np.int16), PB)
+                        out.append(Case(slot, (bd, vfrac, hfrac), dict(bd=bd, w=w, h=h, vfrac=vfrac, hfrac=hfrac, mx=mx, my=my, dist=dist),
+                                        [bd, vfrac, hfrac, d, Buf(plane, 8 * W + 8), W * ps, h, mx, my, w]))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- filters
+
+def _lmcs(slot, g):
+    """Domain: pixels, mapped in place through a 2^bd-entry table of pixels."""
+    out = []
+    for bd in BDS:
+        for (w, h) in shapes(g, [(2, 2), (4, 4), (128, 8), (100, 7), (8, 16), (64, 2)], range(2, 129), range(2, 17)):
+            for dist in DISTS:
+                dw = w + 8
+                img = pixels(g, (h + 2, dw), bd, dist)
+                lut = pixels(g, (1 << bd,), bd, "uniform" if dist in ("uniform", "checker") else dist)
+                out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, dist=dist), [bd, Buf(img, dw + 4), dw * img.itemsize, w, h, Buf(lut)]))
+    return out
+
+
+ALF_PAD = 8
+
+
+def alf_clips(bd):
+    return np.array([1 << bd, 1 << (bd - 3), 1 << (bd - 5), 1 << (bd - 7)], np.int16)
+
+
+def _alf_coeff(g, shape, bd, kind):
+    """ALF coefficients: luma / chroma in [-128, 128] (alf_luma_coeff_abs, alf_chroma_coeff_abs <= 128 with a sign, 7.4.3.18: +128
+    does not fit 8 bits); extremes pair with the smallest clip."""
+    clips = alf_clips(bd)
+    if kind == "uniform":
+        return g.ints(-128, 129, shape).astype(np.int16), clips[g.ints(0, 4, shape)].astype(np.int16)
+    coeff = field(g, shape, -128, 128, kind, np.int16)
+    return coeff, np.full(shape, clips[3], np.int16)
+
+
+def _alf_filter(slot, g):
+    """Domain: pixels with an 8-sample apron; vb_pos inside, at and beyond the block; coefficients / clips as _alf_coeff."""
+    luma = slot == "alf_filter_luma"
+    out = []
+    for bd in BDS:
+        for (w, h) in shapes(g, [(4, 4), (8, 4), (4, 8), (16, 16), (32, 8), (128, 4), (100, 12)], MULT4, MULT4[:4]):
+            vbs = sorted({h - 4 if luma else h - 2, h, h + 4, 1000, 4 if luma else 2} - {0})
+            for vb in vbs:
+                for dist in DISTS:
+                    kind = DISTS[(len(out) // 4) % 4]
+                    src = pixels(g, (h + 2 * ALF_PAD, w + 2 * ALF_PAD + 8), bd, dist)
+                    W, ps = src.shape[1], src.itemsize
+                    coeff, clip = _alf_coeff(g, ((w // 4) * (h // 4), 12) if luma else (6,), bd, kind)
+                    dw = w + 16
+                    d = Buf(np.full((h + 4, dw), SPX, src.dtype), 2 * dw + 8)
+                    out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, vb_pos=vb, dist=dist, coeff=kind),
+                                    [bd, d, dw * ps, Buf(src, ALF_PAD * W + ALF_PAD), W * ps, w, h, Buf(coeff), Buf(clip), vb]))
+    return out
+
+
+def _alf_cc(slot, g):
+    """Domain: luma pixels with apron, chroma pixels filtered in place; the 7 coefficients are 0 or +-2^k, k <= 6 (alf_cc_*_mapped_coeff_abs, 7.4.3.18)."""
+    out = []
+    for bd in BDS:
+        for (hs, vs) in [(1, 1), (1, 0), (0, 0)]:
+            for (w, h) in shapes(g, [(4, 4), (16, 8), (64, 4), (60, 6)], MULT4[:16], range(4, 17, 2)):
+                for vb in sorted({(h << vs) - 4, h << vs, 1000, 2} - {0}):
+                    for dist in DISTS:
+                        lw, lh = w << hs, h << vs
+                        luma = pixels(g, (lh + 2 * ALF_PAD, lw + 2 * ALF_PAD + 8), bd, dist)
+                        W, ps = luma.shape[1], luma.itemsize
+                        mag = g.ints(0, 8, (7,))
+                        coeff = (np.where(mag == 0, 0, 1 << np.maximum(mag - 1, 0)) * np.where(g.ints(0, 2, (7,)), -1, 1)).astype(np.int16)
+                        if dist in ("min", "max"):
+                            coeff = np.full(7, -64 if dist == "min" else 64, np.int16)
+                        dw = w + 16
+                        dst = pixels(g, (h + 4, dw), bd, "uniform" if dist == "uniform" else "checker")
+                        out.append(Case(slot, (bd, hs, vs), dict(bd=bd, w=w, h=h, hs=hs, vs=vs, vb_pos=vb, dist=dist),
+                                        [bd, Buf(dst, 2 * dw + 8), dw * ps, Buf(luma, ALF_PAD * W + ALF_PAD), W * ps, w, h, hs, vs, Buf(coeff), vb]))
+    return out
+
+
+def smooth(g, shape, bd, amp):
+    """Low-contrast content: a ramp in both directions plus +-amp noise, clipped to the pixel range."""
+    mx = (1 << bd) - 1
+    y, x = np.indices(shape)
+    img = g.ints(0, mx + 1) + x * g.ints(-4, 5) + y * g.ints(-4, 5) + g.ints(-amp, amp + 1, shape)
+    return np.clip(img, 0, mx).astype(px_dtype(bd))
+
+
+def _alf_classify(slot, g):
+    """Domain: pixels with apron; w, h multiples of 4; gradient_tmp is a work area."""
+    out = []
+    for bd in BDS:
+        for (w, h) in shapes(g, [(4, 4), (8, 4), (4, 8), (16, 16), (32, 8), (128, 4), (100, 12)], MULT4, MULT4[:4]):
+            for vb in sorted({h - 4, h, 1000, 8} - {0}):
+                for dist in DISTS + ("smooth",):
+                    shape = (h + 2 * ALF_PAD, w + 2 * ALF_PAD + 8)
+                    src = smooth(g, shape, bd, 6) if dist == "smooth" else pixels(g, shape, bd, dist)
+                    W, ps = src.shape[1], src.itemsize
+                    n = (w // 4) * (h // 4)
+                    grad = Buf(np.zeros(((h + 4) // 2) * ((w + 4) // 2) * 4, np.int32), scratch=True)
+                    out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, vb_pos=vb, dist=dist),
+                                    [bd, Buf(np.full(n, -1, np.int32)), Buf(np.full(n, -1, np.int32)), Buf(src, ALF_PAD * W + ALF_PAD), W * ps, w, h, vb, grad]))
+    return out
+
+
+def _alf_recon(slot, g):
+    """Domain: class 0..24, transpose 0..3, coefficient sets in [-128, 128] (as _alf_coeff), clip indices 0..3, class-to-filter map into 64 sets."""
+    out = []
+    for bd in BDS:
+        for size in (1, 7, 64, 256):
+            for dist in DISTS:
+                cls, tr = g.ints(0, 25, (size,)).astype(np.int32), g.ints(0, 4, (size,)).astype(np.int32)
+                coeff_set = field(g, (64, 12), -128, 128, dist, np.int16)
+                clip_idx = field(g, (25, 12), 0, 3, dist, np.uint8)
+                c2f = g.ints(0, 64, (25,)).astype(np.uint8)
+                out.append(Case(slot, (bd,), dict(bd=bd, size=size, dist=dist),
+                                [bd, Buf(np.zeros((size, 12), np.int16)), Buf(np.zeros((size, 12), np.int16)), Buf(cls), Buf(tr), size,
+                                 Buf(coeff_set), Buf(clip_idx), Buf(c2f)]))
+    return out
+
+
+def sao_offsets(g, bd, kind):
+    """SaoOffsetVal[1..4]: |sao_offset_abs| <= (1 << (min(bd, 10) - 5)) - 1, scaled by << (bd - min(bd, 10)) (7.4.12.3); [0] is 0."""
+    mag = ((1 << (min(bd, 10) - 5)) - 1) << (bd - min(bd, 10))
+    step = 1 << (bd - min(bd, 10))
+    if kind == "uniform":
+        v = g.ints(-(mag // step), mag // step + 1, (4,)) * step
+    else:
+        v = field(g, (4,), -mag, mag, kind, np.int64)
+    return np.concatenate([[0], v]).astype(np.int16)
+
+
+SAO_WIDTHS = [4, 8, 12, 16, 20, 32, 36, 48, 52, 64, 68, 80, 84, 96, 100, 112, 116, 128]      # narrowest and widest of the 9 width classes
+
+
+def _sao(slot, g):
+    """Domain: pixels at the implicit source stride with a one-sample apron; offsets as sao_offsets; band position 0..31."""
+    out = []
+    for bd in BDS:
+        ps = 1 if bd == 8 else 2
+        ss = SAO_SS_BYTES // ps
+        for w in (SAO_WIDTHS if not g.seed else [g.pick(MULT4) for _ in SAO_WIDTHS]):
+            for dist in DISTS:
+                h = g.pick([2, 4, 8, 16])
+                src = pixels(g, (h + 4, ss), bd, dist)
+                if dist == "uniform" and g.ints(0, 2):
+                    src = (src >> 3 << 3).astype(src.dtype)          # plateaus, so that the "equal" comparisons occur
+                sb = Buf(src, 2 * ss + 8)
+                dw = w + 8
+                okind = DISTS[(len(out) + DISTS.index(dist)) % 4]
+                offs = Buf(sao_offsets(g, bd, okind))
+                cls = (bd,)          # the width class follows from the width
+                prm = dict(bd=bd, w=w, h=h, dist=dist, offsets=okind)
+                if slot == "sao_band_filter":
+                    for left in (0, 28 + len(out) % 3, 31, g.ints(1, 28)):          # 28..31: the four bands wrap round 31 -> 0
+                        d = Buf(np.full((h + 2, dw), SPX, src.dtype), dw + 4)
+                        out.append(Case(slot, cls, dict(prm, left_class=left), [bd, d, sb, dw * ps, ss * ps, offs, left, w, h]))
+                elif slot == "sao_edge_filter":
+                    for eo in range(4):
+                        d = Buf(np.full((h + 2, dw), SPX, src.dtype), dw + 4)
+                        out.append(Case(slot, cls, dict(prm, eo=eo), [bd, d, sb, dw * ps, offs, eo, w, h]))
+                elif w in (4, 8, 20, 64, 100, 128) or g.seed:          # the restore does not depend on the width class
+                    for eo in range(4):
+                        for variant in (0, 1):
+                            borders = g.ints(0, 2, (4,)).astype(np.int32)
+                            ve, he, de = (g.ints(0, 2, (n,)).astype(np.uint8) for n in (2, 2, 4))
+                            d = Buf(np.full((h + 2, dw), SPX, src.dtype), dw + 4)
+                            out.append(Case(slot, (bd, variant), dict(prm, eo=eo, variant=variant, borders=borders.tolist(), ve=ve.tolist(), he=he.tolist(), de=de.tolist()),
+                                            [bd, variant, d, sb, dw * ps, ss * ps, offs, eo, Buf(borders), w, h, Buf(ve), Buf(he), Buf(de)]))
+    return out
+
+
+# Table 43 of the standard: beta' and tc' by Q; the slots take these unscaled values and scale them by the bit depth themselves
+TC_TAB = [0] * 18 + [3, 4, 4, 4, 4, 5, 5, 5, 5, 7, 7, 8, 9, 10, 10, 11, 13, 14, 15, 17, 19, 21, 24, 25, 29, 33, 36, 41, 45, 51,
+                     57, 64, 71, 80, 89, 100, 112, 125, 141, 157, 177, 198, 222, 250, 280, 314, 352, 395]
+BETA_TAB = [0] * 16 + list(range(6, 19)) + list(range(20, 90, 2))
+LF_N = 32
+
+
+def lf_picture(g, bd, dist):
+    """32x32 around an edge at (16, 16): extremes as they are, else a smooth ramp with a step across the edge and a little noise."""
+    if dist in DISTS:
+        return pixels(g, (LF_N, LF_N), bd, dist)
+    mx = (1 << bd) - 1
+    y, x = np.indices((LF_N, LF_N))
+    step = g.ints(0, 1 << (bd - 4))
+    img = g.ints(mx // 4, 3 * mx // 4) + ((x >= 16) + (y >= 16)) * step + x * g.ints(-2, 3) + y * g.ints(-2, 3)
+    if dist == "noisy":
+        img = img + g.ints(-(1 << (bd - 6)), (1 << (bd - 6)) + 1, img.shape)
+    return np.clip(img, 0, mx).astype(px_dtype(bd))
+
+
+def _lf(slot, g):
+    """Domain: pixels; beta' / tc' rows of Table 43 (first non-zero and last rows included); luma lengths 1, 2, 3, 5, 7, chroma 0, 1, 3."""
+    out = []
+    chroma = slot == "lf_filter_chroma"
+    for bd in BDS:
+        for dirn in (0, 1):
+            off = 16 * LF_N + 8 if dirn == 0 else 8 * LF_N + 16
+            if slot == "lf_ladf_level":
+                for dist in DISTS + ("step", "noisy"):
+                    img = lf_picture(g, bd, dist)
+                    out.append(Case(slot, (bd, dirn), dict(bd=bd, dir=dirn, dist=dist), [bd, dirn, Buf(img, off), LF_N * img.itemsize], ret=True))
+                continue
+            for dist in ("step", "noisy", "step", "noisy", "uniform", "min", "max", "checker"):
+                for rep in range(12):
+                    img = lf_picture(g, bd, dist)
+                    if rep % 3 == 0:          # first and last table rows (tc' 0 / 3 / 395, beta' 0 / 6 / 88)
+                        q = np.array([g.pick([0, 16, 18, 63, 65]) for _ in range(4)])
+                    else:
+                        q = g.ints(16, 64, (4,))
+                    beta = np.array([BETA_TAB[min(v, 63)] for v in q], np.int32)
+                    tc = np.array([TC_TAB[min(v + 2, 65)] for v in q], np.int32)
+                    lens = [0, 1, 3] if chroma else [1, 2, 3, 5, 7]
+                    if rep % 4 == 1 and not chroma:
+                        lens = [1, 3, 5, 7]
+                    lp = np.array([g.pick(lens) for _ in range(4)], np.uint8)
+                    lq = np.array([g.pick(lens) for _ in range(4)], np.uint8)
+                    if rep % 4 == 2:
+                        lq[:] = 3 if chroma else g.pick([3, 5, 7])
+                        lp[:] = g.pick(lens[1:])
+                    no_p, no_q = (g.ints(0, 4, (4,)) == 0).astype(np.uint8), (g.ints(0, 4, (4,)) == 0).astype(np.uint8)
+                    flag = g.ints(0, 2)          # luma: hor_ctu_edge; chroma: the 4:2:0 "shift" (segments of 2 samples)
+                    out.append(Case(slot, (bd, dirn), dict(bd=bd, dir=dirn, dist=dist, q=q.tolist(), lp=lp.tolist(), lq=lq.tolist(),
+                                                           no_p=no_p.tolist(), no_q=no_q.tolist(), flag=flag),
+                                    [bd, dirn, Buf(img, off), LF_N * img.itemsize, Buf(beta), Buf(tc), Buf(no_p), Buf(no_q), Buf(lp), Buf(lq), flag]))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- transform
+
+DCT2, DST7, DCT8 = 0, 1, 2
+
+
+def coeff_block(g, w, h, nzw, nzh, bits, dist):
+    c = np.zeros((h, w), np.int32)
+    c[:nzh, :nzw] = field(g, (nzh, nzw), -(1 << bits), (1 << bits) - 1, dist, np.int32)
+    return c
+
+
+def itx_ranges(bd):
+    """log2_transform_range 15, and for 12 bit the extended range max(15, min(20, bd + 6)) = 18 as well."""
+    return (15, 18) if bd == 12 else (15,)
+
+
+def _itx(slot, g):
+    """Domain: coefficients in [-2^range, 2^range) inside the nzw x nzh window, zero elsewhere; nz within the zero-out limit (32 DCT-2, 16 DST-7 / DCT-8)."""
+    out = []
+    for bd in BDS:
+        for bits in itx_ranges(bd):
+            for trh in range(3):
+                for trv in range(3):
+                    for lw in range(7):
+                        for lh in range(7):
+                            w, h = 1 << lw, 1 << lh
+                            limw, limh = min(32 if trh == DCT2 else 16, w), min(32 if trv == DCT2 else 16, h)
+                            variants = [(1, 1, "max"), (limw, limh, "checker"), (limw, limh, "uniform"), (limw, limh, "min"),
+                                        (max(1, limw // 2 + (limw > 2)), max(1, limh // 2 + (limh > 2)), "uniform")]
+                            if g.seed:          # the sweep: any window inside the limit
+                                variants[4] = (g.ints(1, limw + 1), g.ints(1, limh + 1), "uniform")
+                            exists = (w > 1 or h > 1) and (trh == DCT2 or 4 <= w <= 32) and (trv == DCT2 or 4 <= h <= 32)
+                            for (nzw, nzh, dist) in (variants if exists else variants[2:3]):
+                                c = coeff_block(g, w, h, nzw, nzh, bits, dist)
+                                out.append(Case(slot, (bd, bits), dict(bd=bd, range=bits, trh=trh, trv=trv, w=w, h=h, nzw=nzw, nzh=nzh, dist=dist),
+                                                [trh, trv, lw, lh, Buf(c), nzw, nzh, bits, bd], ret=True))
+    return out
+
+
+def _inv_tx_1d(slot, g):
+    """Domain: one strided vector of n coefficients in [-2^15, 2^15) (and 2^18), the first nz non-zero; and the type / size pairs
+    that have no kernel, which return -1 and leave the vector alone."""
+    out = []
+    for (typ, n) in [(DST7, 2), (DST7, 64), (DCT8, 2), (DCT8, 64)]:
+        c = field(g, (n,), -(1 << 15), (1 << 15) - 1, "uniform", np.int32)
+        out.append(Case(slot, (0, typ), dict(type=typ, n=n, nz=1, stride=1, bits=15, dist="uniform", kernel="none"), [typ, n, Buf(c), 1, 1], ret=True))
+    for typ in range(3):
+        for n in ([1, 2, 4, 8, 16, 32, 64] if typ == DCT2 else [1, 4, 8, 16, 32]):
+            lim = min(n, 32 if typ == DCT2 else 16)
+            for nz in sorted({1, lim, max(1, lim // 2 + (lim > 2))}):
+                for stride in (1, n, 7):
+                    for bits in (15, 18):
+                        for dist in DISTS:
+                            c = np.zeros(n * stride + 3, np.int32)
+                            c[:nz * stride:stride] = field(g, (nz,), -(1 << bits), (1 << bits) - 1, dist, np.int32)
+                            out.append(Case(slot, (0, typ), dict(type=typ, n=n, nz=nz, stride=stride, bits=bits, dist=dist), [typ, n, Buf(c), stride, nz], ret=True))
+    return out
+
+
+def _lfnst(slot, g):
+    """Domain: 8 or 16 inputs in [-2^range, 2^range); intra modes -14..80 (after wide-angle mapping); sets 1 and 2; 16- and 48-output kernels."""
+    out = []
+    for (n_tr_s, nz) in ((16, 8), (16, 16), (48, 8), (48, 16)):
+        for mode in range(-14, 81):
+            for idx in (1, 2):
+                dist = dist_cycle(len(out))
+                bits = 15 if len(out) % 5 else 18
+                u = field(g, (16,), -(1 << bits), (1 << bits) - 1, dist, np.int32)
+                out.append(Case(slot, (0, n_tr_s, nz), dict(n_tr_s=n_tr_s, nz=nz, mode=mode, lfnst_idx=idx, range=bits, dist=dist),
+                                [Buf(np.zeros(48, np.int32)), Buf(u), nz, n_tr_s, mode, idx, bits]))
+    return out
+
+
+RES_SHAPES = [(4, 4), (8, 2), (2, 8), (32, 4), (64, 2), (4, 64), (1, 16), (16, 1), (64, 16)]
+
+
+def _residual(slot, g):
+    """Domain: residuals in [-2^(bd+1), 2^(bd+1)) on pixels; joint Cb-Cr sign +-1 and shift 0..1 (8.7.2)."""
+    out = []
+    bds = BDS if slot != "pred_residual_joint" else (10,)
+    for bd in bds:
+        for (w, h) in shapes(g, RES_SHAPES, [1] + POW2[:6], POW2[:6]):
+            for dist in DISTS:
+                for (c_sign, shift) in ([(1, 0), (-1, 0), (1, 1), (-1, 1)] if slot != "add_residual" else [(0, 0)]):
+                    res = field(g, (h, w), -(1 << (bd + 1)), (1 << (bd + 1)) - 1, dist, np.int32)
+                    prm = dict(bd=bd, w=w, h=h, dist=dist, c_sign=c_sign, shift=shift)
+                    if slot == "pred_residual_joint":
+                        out.append(Case(slot, (0,), prm, [Buf(res), w, h, c_sign, shift]))
+                        continue
+                    dw = w + 8
+                    pred = pixels(g, (h + 2, dw), bd, "uniform" if dist == "uniform" else DISTS[1 + (DISTS.index(dist) + (c_sign > 0)) % 3])
+                    args = [bd, Buf(pred, dw + 4), Buf(res), w, h, dw * pred.itemsize] + ([c_sign, shift] if slot == "add_residual_joint" else [])
+                    out.append(Case(slot, (bd,), prm, args))
+    return out
+
+
+def _bdpcm(slot, g):
+    """Domain: levels whose running sums reach the clip at +-2^range (extremes) or stay inside it (uniform); both directions; blocks up to 32x32."""
+    out = []
+    for bits in (15, 18):
+        for (w, h) in shapes(g, [(4, 4), (8, 2), (2, 8), (32, 4), (4, 32), (32, 32), (16, 8)], POW2[:5], POW2[:5]):
+            for vertical in (0, 1):
+                for dist in DISTS:
+                    c = field(g, (h, w), -(1 << bits), (1 << bits) - 1, dist, np.int32)
+                    out.append(Case(slot, (0, bits), dict(w=w, h=h, vertical=vertical, range=bits, dist=dist), [Buf(c), w, h, vertical, bits]))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- intra
+
+INTRA_SIZES = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 16), (16, 4), (8, 32), (32, 8), (64, 16), (16, 64), (4, 64), (64, 4),
+               (2, 8), (8, 2), (2, 2), (4, 8), (8, 4), (2, 4), (4, 2), (2, 16), (16, 2), (2, 32), (32, 2), (8, 16), (16, 8), (8, 64), (64, 8),
+               (16, 32), (32, 16), (32, 64), (64, 32), (4, 32), (32, 4), (2, 64), (64, 2)]
+EORG = 160          # origin of the edge arrays: room for the negative indices of the angular predictors
+ELEN = 448          # and for the 2 * size + reference-line tail on the far side
+ISTRIDE = 72
+
+
+def wide_angle(mode, w, h):
+    """The wide-angle mapping of a non-ISP block (pinned against the reference through intra_wide_angle)."""
+    lg = lambda v: v.bit_length() - 1
+    ratio = abs(lg(w) - lg(h))
+    mx, mn = (8 + 2 * ratio, 60 - 2 * ratio) if ratio > 1 else (8, 60)
+    if w > h and 2 <= mode < mx:
+        return mode + 65
+    if h > w and mn < mode <= 66:
+        return mode - 67
+    return mode
+
+
+def need_pdpc(w, h, mode):
+    """PDPC eligibility of an angular mode with reference line 0 and no BDPCM (the slot's need_pdpc argument may be 1 only then: the
+    predictors shift by nscale, which is negative otherwise).  Checked against the reference's own helper by the intra_need_pdpc list."""
+    if w < 4 or h < 4 or 18 < mode < 50:
+        return False
+    a = abs(_angle(mode))
+    inv = (16384 + a // 2) // a
+    side = h if mode >= 50 else w
+    return min(2, side.bit_length() - (3 * inv - 2).bit_length() + 8) >= 0
+
+
+def _edges(g, bd, dist):
+    return Buf(pixels(g, (ELEN,), bd, dist), EORG), Buf(pixels(g, (ELEN,), bd, dist if dist != "checker" else "uniform"), EORG)
+
+
+def _intra_dst(bd, h):
+    return Buf(np.full((h + 2, ISTRIDE), SPX, px_dtype(bd)), ISTRIDE + 4)
+
+
+def _intra_simple(slot, g):
+    """Domain: reference samples = pixels; every block shape 2x2 .. 64x64; stride in pixels."""
+    out = []
+    for bd in BDS:
+        for (w, h) in INTRA_SIZES:
+            for dist in DISTS:
+                top, left = _edges(g, bd, dist)
+                edge = {"pred_planar": [top, left], "pred_dc": [top, left], "pred_v": [top], "pred_h": [left]}[slot]
+                out.append(Case(slot, (bd,), dict(bd=bd, w=w, h=h, dist=dist), [bd, _intra_dst(bd, h)] + edge + [w, h, ISTRIDE]))
+    return out
+
+
+def _intra_mip(slot, g):
+    """Domain: reference samples = pixels; luma blocks 4..64 a side; every mode of the block's size id, both transposes."""
+    out = []
+    for bd in BDS:
+        for (w, h) in [s for s in INTRA_SIZES if min(s) >= 4]:
+            size_id = 0 if (w, h) == (4, 4) else 1 if (w == 4 or h == 4 or (w, h) == (8, 8)) else 2
+            for mode in range((16, 8, 6)[size_id]):
+                for tr in (0, 1):
+                    dist = dist_cycle(len(out))
+                    top, left = _edges(g, bd, dist)
+                    out.append(Case(slot, (bd, size_id), dict(bd=bd, w=w, h=h, mode=mode, transpose=tr, dist=dist),
+                                    [bd, _intra_dst(bd, h), top, left, w, h, ISTRIDE, mode, tr]))
+    return out
+
+
+def _intra_angular(slot, g):
+    """Domain: reference samples = pixels; every shape; every angular mode reachable through the wide-angle mapping of the shape
+    (without 18 / 50, which go to pred_h / pred_v); luma needs 4 samples a side and may use reference lines 1 and 2."""
+    vertical = slot == "pred_angular_v"
+    out = []
+    for bd in BDS:
+        for (w, h) in [s for s in INTRA_SIZES if max(s) <= 16 * min(s)]:          # the mode tables end at -14 / 80: aspect ratio 16
+            modes = sorted({wide_angle(m, w, h) for m in range(2, 67)} - {18, 50})
+            for mode in [m for m in modes if (m >= 34) == vertical]:
+                pd = int(need_pdpc(w, h, mode))
+                k = len(out) + g.seed          # another seed rotates the variants too
+                # chroma, and for luma one of: plain, filtered, filtered + PDPC, reference line 1 / 2 (the sweep of the live-reference test draws all of them)
+                variants = [(1, 0, k & 1, pd if k & 2 else 0)] if (k + BDS.index(bd)) % 3 == 0 or min(w, h) < 4 else []
+                if min(w, h) >= 4:
+                    variants.append([(0, 0, 0, pd), (0, 0, 1, 0), (0, 0, 1, pd), (0, 1, 0, 0), (0, 2, 1, 0), (0, 0, 0, 0)][(k // 2 + mode) % 6])
+                for (c_idx, ref_idx, ff, pdpc) in variants:
+                    dist = dist_cycle(len(out))
+                    top, left = _edges(g, bd, dist)
+                    out.append(Case(slot, (bd, c_idx), dict(bd=bd, w=w, h=h, mode=mode, c_idx=c_idx, ref_idx=ref_idx, filter_flag=ff, need_pdpc=pdpc, dist=dist),
+                                    [bd, _intra_dst(bd, h), top, left, w, h, ISTRIDE, c_idx, mode, ref_idx, ff, pdpc]))
+    return out
+
+
+def _intra_helpers(slot, g):
+    """Domain: the whole argument space the decoder can reach (modes -14..80, block sides 1..64 as powers of two).  The lists of
+    the slots in EXHAUSTIVE hold every argument tuple of that domain; intra_need_pdpc and intra_wide_angle hold every shape and
+    mode with a choice of the other arguments, and their sweep draws all arguments at random."""
+    out = []
+    sides = [1, 2, 4, 8, 16, 32, 64]
+    legal = [(w, h) for w in sides[1:] for h in sides[1:] if max(w, h) <= 16 * min(w, h)]
+    if g.seed and slot == "intra_need_pdpc":
+        for _ in range(2048):
+            (w, h), (bdpcm, ref_idx) = g.pick(legal), g.pick([(0, 0), (0, 0), (1, 0), (0, 1), (0, 2)])
+            m = g.pick(sorted({wide_angle(m, w, h) for m in range(2, 67)} | {0, 1}))
+            out.append(Case(slot, (0,), dict(w=w, h=h, mode=m, bdpcm=bdpcm, ref_idx=ref_idx), [w, h, bdpcm, m, ref_idx], ret=True))
+        return out
+    if g.seed and slot == "intra_wide_angle":
+        for _ in range(2048):
+            (w, h), (cw, ch), isp, c_idx, m = g.pick(legal), g.pick(legal), g.ints(0, 2), g.ints(0, 3), g.ints(0, 67)
+            if not isp:
+                cw, ch = w, h
+            out.append(Case(slot, (0,), dict(tb=(w, h), cb=(cw, ch), isp=isp, c_idx=c_idx, mode=m), [isp, c_idx, w, h, cw, ch, m], ret=True))
+        return out
+    if slot == "intra_pred_angle":
+        out = [Case(slot, (0,), dict(mode=m), [m], ret=True) for m in range(-14, 81)]
+    elif slot == "intra_inv_angle":
+        angles = sorted({a for a in (abs(_angle(m)) for m in range(-14, 81)) if a})
+        out = [Case(slot, (0,), dict(angle=s * a), [s * a], ret=True) for a in angles for s in (1, -1)]
+    elif slot == "intra_ref_filter_flag":
+        out = [Case(slot, (0,), dict(mode=m), [m], ret=True) for m in range(-14, 84)]
+    elif slot == "intra_mip_size_id":
+        out = [Case(slot, (0,), dict(w=w, h=h), [w, h], ret=True) for w in sides[2:] for h in sides[2:]]
+    elif slot == "intra_nscale":
+        for w in sides[1:]:
+            for h in [v for v in sides[1:] if max(w, v) <= 16 * min(w, v)]:
+                for m in sorted({wide_angle(m, w, h) for m in range(2, 67)} | {0, 1}):
+                    if not 18 < m < 50:
+                        out.append(Case(slot, (0,), dict(w=w, h=h, mode=m), [w, h, m], ret=True))
+    elif slot == "intra_need_pdpc":
+        for w in sides[1:]:
+            for h in [v for v in sides[1:] if max(w, v) <= 16 * min(w, v)]:
+                for m in sorted({wide_angle(m, w, h) for m in range(2, 67)} | {0, 1}):
+                    for (bdpcm, ref_idx) in [(0, 0)] + ([((1, 0), (0, 1), (0, 2))[len(out) % 3]] if m % 4 == 2 else []):
+                        out.append(Case(slot, (0,), dict(w=w, h=h, mode=m, bdpcm=bdpcm, ref_idx=ref_idx), [w, h, bdpcm, m, ref_idx], ret=True))
+    elif slot == "intra_wide_angle":          # the mapping depends on the sign and size of log2(w / h): one shape per ratio, and a few more
+        for (w, h) in [(64, 2 << k) for k in range(6)] + [(2 << k, 64) for k in range(5)] + [(4, 8), (32, 16), (8, 8), (2, 2)]:
+            for m in range(0, 67):
+                out.append(Case(slot, (0,), dict(tb=(w, h), mode=m), [0, 0, w, h, w, h, m], ret=True))
+                cw, ch = sides[1 + (w + m) % 6], sides[1 + (h + 3 * m) % 6]
+                if m % 3 == 0:
+                    out.append(Case(slot, (0,), dict(tb=(w, h), cb=(cw, ch), isp=1, c_idx=m & 1, mode=m), [1, m & 1, w, h, cw, ch, m], ret=True))
+    return out
+
+
+def _angle(mode):
+    """intraPredAngle of Table 24 (only used to enumerate the arguments of intra_inv_angle)."""
+    t = [0, 1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 23, 26, 29, 32, 35, 39, 45, 51, 57, 64, 73, 86, 102, 128, 171, 256, 341, 512]
+    idx = mode - 50 if mode > 34 else 18 - mode if mode > 0 else 16 - mode
+    return -t[-idx] if idx < 0 else t[idx]
+
+
+# ---------------------------------------------------------------------------------------------------------------- registry
+
+# slot -> (builder, ctypes signature or None when ffvvc_amd.abi.SLOT_SIGNATURES has it, exported by the product library)
+HELPER_SIGNATURES = {
+    "inv_tx_1d":             ("i", "iipqz"),
+    "intra_pred_angle":      ("i", "i"),
+    "intra_inv_angle":       ("i", "i"),
+    "intra_nscale":          ("i", "iii"),
+    "intra_need_pdpc":       ("i", "iiiii"),
+    "intra_ref_filter_flag": ("i", "i"),
+    "intra_mip_size_id":     ("i", "ii"),
+    "intra_wide_angle":      ("i", "iiiiiii"),
+}
+
+BUILDERS = {
+    "put": _put_like, "put_uni": _put_like, "put_uni_w": _put_like,
+    "avg": _blend, "w_avg": _blend, "put_ciip": _put_ciip, "put_gpm": _put_gpm,
+    "fetch_samples": _fetch, "bdof_fetch_samples": _fetch, "prof_grad_filter": _prof_grad,
+    "apply_prof": _apply_prof, "apply_prof_uni": _apply_prof, "apply_prof_uni_w": _apply_prof,
+    "apply_bdof": _apply_bdof, "sad": _sad, "dmvr": _dmvr,
+    "lmcs_filter": _lmcs,
+    "alf_filter_luma": _alf_filter, "alf_filter_chroma": _alf_filter, "alf_filter_cc": _alf_cc,
+    "alf_classify": _alf_classify, "alf_recon_coeff_and_clip": _alf_recon,
+    "sao_band_filter": _sao, "sao_edge_filter": _sao, "sao_edge_restore": _sao,
+    "lf_filter_luma": _lf, "lf_filter_chroma": _lf, "lf_ladf_level": _lf,
+    "itx": _itx, "inv_lfnst_1d": _lfnst, "add_residual": _residual, "add_residual_joint": _residual,
+    "pred_residual_joint": _residual, "transform_bdpcm": _bdpcm,
+    "pred_planar": _intra_simple, "pred_dc": _intra_simple, "pred_v": _intra_simple, "pred_h": _intra_simple,
+    "pred_angular_v": _intra_angular, "pred_angular_h": _intra_angular, "pred_mip": _intra_mip,
+    "inv_tx_1d": _inv_tx_1d,
+    "intra_pred_angle": _intra_helpers, "intra_inv_angle": _intra_helpers, "intra_nscale": _intra_helpers,
+    "intra_need_pdpc": _intra_helpers, "intra_ref_filter_flag": _intra_helpers, "intra_mip_size_id": _intra_helpers,
+    "intra_wide_angle": _intra_helpers,
+}
+SLOTS = tuple(BUILDERS)
+EXHAUSTIVE = ("intra_pred_angle", "intra_inv_angle", "intra_nscale", "intra_ref_filter_flag", "intra_mip_size_id")      # whole domain listed: no sweep
+DEVICE_SLOTS = tuple(s for s in SLOTS if s not in HELPER_SIGNATURES)      # the product exports the DSP slots, not the helpers
+NO_BD_SLOTS = ("sad", "inv_lfnst_1d", "pred_residual_joint", "transform_bdpcm") + tuple(HELPER_SIGNATURES)      # their group keys start with 0
+
+
+def slot_bds(slot):
+    """First element of the slot's group keys: the bit depths it is listed at, or (0,) when it takes none."""
+    return (0,) if slot in NO_BD_SLOTS else BDS
+
+
+def cases(slot, seed=0):
+    return BUILDERS[slot](slot, Gen(slot, seed))
+
+
+def signatures():
+    from ffvvc_amd import abi
+    table = {s: abi.SLOT_SIGNATURES[s] for s in SLOTS if s in abi.SLOT_SIGNATURES}
+    table.update(HELPER_SIGNATURES)
+    return table
+
+
+def bind(lib, prefix, slots=SLOTS):
+    from ffvvc_amd import abi
+    table = signatures()
+    abi.bind(lib, prefix, {s: table[s] for s in slots})
+    return lib
+
+
+# ---------------------------------------------------------------------------------------------------------------- running
+
+def run(case, fn):
+    """Call `fn` on private copies of the case's buffers; returns (buffers after the call, return value or None)."""
+    bufs, argv = [], []
+    for a in case.args:
+        if isinstance(a, Buf):
+            c = a.arr.copy()
+            bufs.append(c)
+            argv.append(c.ctypes.data + a.off * c.itemsize)
+        else:
+            argv.append(int(a))
+    r = fn(*argv)
+    return bufs, (int(r) if case.ret else None)
+
+
+def outputs(case, bufs, ret):
+    """What counts as the slot's result: every buffer that is no work area (inputs included: they must come back untouched) and the return value."""
+    res = [b for a, b in zip([a for a in case.args if isinstance(a, Buf)], bufs) if not a.scratch]
+    if case.ret:
+        res.append(np.array([ret], np.int64))
+    return res
+
+
+def first_difference(case, want, got):
+    """Readable account of the first differing sample between two `outputs` lists, or None."""
+    for i, (x, y) in enumerate(zip(want, got)):
+        if not np.array_equal(x, y):
+            bad = np.argwhere(x != y)
+            at = tuple(bad[0])
+            return f"{case.slot} {case.params}: output #{i} differs in {len(bad)} elements, first at {list(map(int, at))}: want {x[at]} got {y[at]}"
+    return None
+
+
+def groups(slot, seed=0):
+    """The case list cut into digest groups: [(group id, [cases])], at most GROUP cases each, grouped by (slot, bit depth, index tuple)."""
+    by_key = {}
+    for c in cases(slot, seed):
+        by_key.setdefault(c.key, []).append(c)
+    out = []
+    for key, lst in by_key.items():
+        for k in range(0, len(lst), GROUP):
+            out.append((f"{slot}/" + ".".join(str(v) for v in key) + f"/{k // GROUP}", lst[k:k + GROUP]))
+    return out
+
+
+def input_digest(hasher, case):
+    for a in case.args:
+        if isinstance(a, Buf):
+            hasher.update(f"{a.arr.dtype.str}{a.arr.shape}@{a.off};".encode())
+            hasher.update(a.arr.tobytes())
+        else:
+            hasher.update(f"i{int(a)};".encode())
+
+
+def output_digest(hasher, outs):
+    for o in outs:
+        hasher.update(np.ascontiguousarray(o).tobytes())

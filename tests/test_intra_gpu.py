@@ -9,21 +9,10 @@ import pytest
 
 from conftest import P, px_dtype, rand_pixels
 from ffvvc_amd import abi
+from ref_cases import wide_angle          # the wide-angle mapping of a non-ISP block, pinned against the reference by test_oracle_ref_cpu.py
 
 pytestmark = pytest.mark.gpu
 ORG = 512
-
-
-def wide_angle(mode, w, h):
-    """ff_vvc_wide_angle_mode_mapping (vvc_intra.c:693) for a non-ISP block."""
-    ratio = abs(int(np.log2(w)) - int(np.log2(h)))
-    mx = 8 + 2 * ratio if ratio > 1 else 8
-    mn = 60 - 2 * ratio if ratio > 1 else 60
-    if w > h and 2 <= mode < mx:
-        return mode + 65
-    if h > w and mn < mode <= 66:
-        return mode - 67
-    return mode
 
 
 def edges(rng, bd):

@@ -1,5 +1,5 @@
-"""CPU: properties of the oracle that hold independently of both implementations (the oracle is parity-unpinned — the
-reference cannot be built here and its tests hold no golden vectors — so these are the strongest checks available):
+"""CPU: properties of the oracle that hold independently of both implementations (for the callers and context-taking slots, which
+are not pinned against the reference, these are the strongest checks available; the leaf slots are pinned by test_oracle_ref_cpu.py):
 transform-matrix identities, DC gains on flat input, identity cases, mode-helper tables."""
 import ctypes
 

@@ -1,0 +1,68 @@
+#!/usr/bin/env python3
+"""Regenerate tests/golden/ref_slots.json: SHA-256 digests of what the reference's own C path computes on the case lists
+of tests/ref_cases.py.
+
+Needs oracle/_ref/libvvcref.so (`make -C oracle ref`, or __graft_entry__.build() where the reference tree is present).
+For every group of at most 64 cases (slot, bit depth, table indices) the file holds [digest of the concatenated inputs,
+digest of the concatenated outputs]; it holds no samples.  Usage: python tools/gen_golden.py [--check]"""
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import ref_cases  # noqa: E402
+import ref_lib    # noqa: E402
+
+PATH = ref_lib.GOLDEN_PATH
+
+
+def group_digests(cases, fn):
+    """(input digest, output digest) of one group run through `fn`."""
+    h_in, h_out = hashlib.sha256(), hashlib.sha256()
+    for c in cases:
+        ref_cases.input_digest(h_in, c)
+        ref_cases.output_digest(h_out, ref_cases.outputs(c, *ref_cases.run(c, fn)))
+    return h_in.hexdigest(), h_out.hexdigest()
+
+
+def generate(lib, prefix):
+    doc = {"source": "reference C path (ff_vvc_dsp_init slots and vvc_intra.c / vvc_itx_1d.c helpers) through oracle/ref_shim.c on tests/ref_cases.py",
+           "format": "slots[slot][group] = [sha256 of inputs, sha256 of outputs]; group = bit depth and table indices / chunk of 64 cases",
+           "slots": {}}
+    for slot in ref_cases.SLOTS:
+        fn = getattr(lib, prefix + slot)
+        doc["slots"][slot] = {gid.split("/", 1)[1]: list(group_digests(cases, fn)) for gid, cases in ref_cases.groups(slot)}
+    return doc
+
+
+def dumps(doc):
+    lines = ["{", f' "source": {json.dumps(doc["source"])},', f' "format": {json.dumps(doc["format"])},', ' "slots": {']
+    slots = list(doc["slots"].items())
+    for i, (slot, grp) in enumerate(slots):
+        lines.append(f"  {json.dumps(slot)}: {{")
+        items = list(grp.items())
+        lines += [f"   {json.dumps(k)}: {json.dumps(v, separators=(',', ':'))}" + ("," if j + 1 < len(items) else "") for j, (k, v) in enumerate(items)]
+        lines.append("  }" + ("," if i + 1 < len(slots) else ""))
+    lines += [" }", "}", ""]
+    return "\n".join(lines)
+
+
+def main():
+    lib = ref_lib.load()
+    if lib is None:
+        sys.exit(f"{ref_lib.LIB_PATH} is missing: run `make -C oracle ref` where the reference tree is present")
+    text = dumps(generate(lib, "ref_"))
+    if "--check" in sys.argv:
+        with open(PATH) as f:
+            sys.exit(0 if f.read() == text else "tests/golden/ref_slots.json is stale")
+    with open(PATH, "w") as f:
+        f.write(text)
+    n = sum(len(g) for g in json.loads(text)["slots"].values())
+    print(f"wrote {PATH}: {n} groups, {len(text)} bytes")
+
+
+if __name__ == "__main__":
+    main()
