@@ -158,6 +158,8 @@ BATCH_SIGNATURES = {
     "inter_tb_pass":    ("i", "pppi"),
     # the transform-skip / BDPCM blocks from 16-byte records (vvc355_ts_tu): BDPCM on the levels + scaling + (scaled, joint) residual add
     "ts_tb_pass":       ("i", "pppi"),
+    # boundary strengths and luma filter lengths straight from the unit records of tab_fill_pass (vvc355_bs_rec_frame): no side tables
+    "deblock_bs_rec_pass": ("i", "ppp"),
 }
 
 
@@ -660,6 +662,24 @@ class TabFill(ctypes.Structure):
                 ("tb_pos_x0", ctypes.c_uint64 * 2), ("tb_pos_y0", ctypes.c_uint64 * 2), ("tb_width", ctypes.c_uint64 * 2), ("tb_height", ctypes.c_uint64 * 2),
                 ("cb_pos_x", ctypes.c_uint64), ("cb_pos_y", ctypes.c_uint64), ("cb_width", ctypes.c_uint64), ("cb_height", ctypes.c_uint64),
                 ("msf", ctypes.c_uint64), ("iaf", ctypes.c_uint64)]
+
+
+class BsRecFrame(ctypes.Structure):
+    """Mirror of vvc355_bs_rec_frame."""
+    _fields_ = [("cu", ctypes.c_uint64), ("tu", ctypes.c_uint64), ("ctu_first_cu", ctypes.c_uint64), ("ctu_first_tu", ctypes.c_uint64),
+                ("mvf", ctypes.c_uint64), ("ref_poc", ctypes.c_uint64), ("slice_idx", ctypes.c_uint64),
+                ("ctb_to_col_bd", ctypes.c_uint64), ("ctb_to_row_bd", ctypes.c_uint64),
+                ("bs", (ctypes.c_uint64 * 3) * 2), ("max_len_p", ctypes.c_uint64 * 2), ("max_len_q", ctypes.c_uint64 * 2),
+                ("tb_width_c", ctypes.c_uint64), ("tb_height_c", ctypes.c_uint64),
+                ("n_cu", ctypes.c_int32), ("n_tu", ctypes.c_int32), ("unit_pitch", ctypes.c_int32), ("mvf_pitch", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ctb_width", ctypes.c_int32), ("ctb_height", ctypes.c_int32),
+                ("ctb_log2", ctypes.c_uint8), ("hs", ctypes.c_uint8), ("vs", ctypes.c_uint8), ("n_comp", ctypes.c_uint8),
+                ("lfase", ctypes.c_uint8), ("lfate", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 2)]
+
+
+# what vvc355_deblock_bs_rec_pass returns for a frame it refuses (VVC355_BS_REC_E_*)
+(BS_REC_E_FRAME, BS_REC_E_SIZE, BS_REC_E_CTB, BS_REC_E_GRID, BS_REC_E_PITCH, BS_REC_E_COMP, BS_REC_E_SHIFT, BS_REC_E_COUNT,
+ BS_REC_E_RECORDS, BS_REC_E_TABLES, BS_REC_E_OUTPUT) = -1, -2, -3, -4, -5, -6, -7, -8, -9, -10, -11
 
 
 class LmcsResidJob(ctypes.Structure):

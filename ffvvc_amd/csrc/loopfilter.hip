@@ -6,6 +6,7 @@
 // stage the caller's border rules libavcodec/vvc/vvc_filter.c:154-300.
 #include "common.hpp"
 #include "runtime.hpp"
+#include "bs_rules.hpp"
 #include "../../include/vvc_mi355.h"
 
 namespace vvc355 {
@@ -977,46 +978,7 @@ static void slot_deblock(int bd, int dir, int chroma, uint8_t *pix, ptrdiff_t st
 
 // ---------------------------------------------------------------------------------------------- boundary strengths
 
-// boundary_strength (vvc_filter.c:308-372): the motion rule between two inter blocks.  pc / pn = reference POC lists of the
-// slices the two blocks belong to (int32 [2][32]).
-__device__ __forceinline__ bool mv_far(const int32_t *a, const int32_t *b) { return abs(a[0] - b[0]) >= 8 || abs(a[1] - b[1]) >= 8; }
-
-__device__ __forceinline__ int bs_motion(const vvc355_mvfield &c, const vvc355_mvfield &n, const int *pc, const int *pn)
-{
-    if (c.pred_flag == 3 && n.pred_flag == 3) {
-        const int c0 = gld<int>(pc + c.ref_idx[0]), c1 = gld<int>(pc + 32 + c.ref_idx[1]);
-        const int n0 = gld<int>(pn + n.ref_idx[0]), n1 = gld<int>(pn + 32 + n.ref_idx[1]);
-        if (c0 == n0 && c0 == c1 && n0 == n1)
-            return (mv_far(n.mv[0], c.mv[0]) || mv_far(n.mv[1], c.mv[1])) && (mv_far(n.mv[1], c.mv[0]) || mv_far(n.mv[0], c.mv[1]));
-        if (n0 == c0 && n1 == c1)
-            return mv_far(n.mv[0], c.mv[0]) || mv_far(n.mv[1], c.mv[1]);
-        if (n1 == c0 && n0 == c1)
-            return mv_far(n.mv[1], c.mv[0]) || mv_far(n.mv[0], c.mv[1]);
-        return 1;
-    }
-    if (c.pred_flag != 3 && n.pred_flag != 3) {
-        const bool c_l0 = c.pred_flag & 1, n_l0 = n.pred_flag & 1;
-        const int ra = gld<int>(pc + (c_l0 ? c.ref_idx[0] : 32 + c.ref_idx[1]));
-        const int rb = gld<int>(pn + (n_l0 ? n.ref_idx[0] : 32 + n.ref_idx[1]));
-        if (ra != rb)
-            return 1;
-        const int ax = c_l0 ? c.mv[0][0] : c.mv[1][0], ay = c_l0 ? c.mv[0][1] : c.mv[1][1];
-        const int bx = n_l0 ? n.mv[0][0] : n.mv[1][0], by = n_l0 ? n.mv[0][1] : n.mv[1][1];
-        return abs(ax - bx) >= 8 || abs(ay - by) >= 8;
-    }
-    return 1;
-}
-
-__device__ __forceinline__ vvc355_mvfield ld_mvf(const vvc355_mvfield *p)
-{
-    uint64_t w[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) w[i] = gld<uint64_t>((const uint64_t *)p + i);
-    vvc355_mvfield r;
-    __builtin_memcpy(&r, w, 24);
-    return r;
-}
-
+// (mv_far, bs_motion and ld_mvf are bs_rules.hpp; the rules of phase 3 are bs_rules_body.inc: bs_rec.hip derives the same from records)
 // One lane per 4x4 luma unit; both edge directions (dir 1 = vertical edges: neighbour on the left, dir 0 = horizontal edges:
 // neighbour above).  Gather form of vvc_deblock_bs (vvc_filter.c:756-783): the unit asks which rule of the transform unit
 // covering it wrote its entry in the reference's scatter loops.
@@ -1088,64 +1050,9 @@ __global__ __launch_bounds__(256) void deblock_bs_kernel(const vvc355_bs_frame *
     const bool sb_cu = !is_intra && (gld<uint8_t>((const uint8_t *)F.msf + cbo) | gld<uint8_t>((const uint8_t *)F.iaf + cbo));
 
     // ---- phase 3: the rules
-#pragma unroll
-    for (int dir = 0; dir < 2; dir++) {
-        const int a = dir ? x : y;                              // coordinate across the edge
-        // a CTB edge that must not be filtered (:498-507, :583-591)
-        const bool ctb_edge_off = (!F.lfase && n_slice[dir] != my_slice) || (!F.lfate && tile_edge[dir]);
-        const bool strong = curr.pred_flag == 0 || neigh[dir].pred_flag == 0 || curr.ciip_flag || neigh[dir].ciip_flag;
-        // ---- luma tree
-        int bs = 0, len_p = 0, len_q = 0;
-        const bool has_sb = sb_cu && cb_size[dir] > 8;
-        if (a == t0[0][dir]) {
-            if (a > 0 && !ctb_edge_off) {
-                // transform-block edge (:509-545)
-                const int off_c = cb0[dir] - a;
-                if (fn[dir][0] && fq[0])
-                    bs = 0;
-                else if (strong)
-                    bs = 2;
-                else if (fq[1] || fn[dir][1])
-                    bs = 1;
-                else if (off_c && ((off_c & 7) || !has_sb))
-                    bs = 0;
-                else
-                    bs = bs_motion(curr, neigh[dir], (const int *)F.ref_poc + my_slice * 64, (const int *)F.ref_poc + n_slice[dir] * 64);
-                // derive_max_filter_length_luma (:374-397)
-                if (size_p[dir] <= 4 || size_q[dir] <= 4) {
-                    len_p = len_q = 1;
-                } else {
-                    len_p = size_p[dir] >= 32 ? 7 : 3;
-                    len_q = size_q[dir] >= 32 ? 7 : 3;
-                }
-                if (has_sb)
-                    len_q = min(5, len_q);
-                if (sb_p[dir])
-                    len_p = min(5, len_p);
-            }
-        } else if (sb_cu && !((a - cb0[dir]) & 7)) {
-            // sub-block edge inside the transform unit (:399-475), both sides in the current slice
-            const int *rpl = (const int *)F.ref_poc + my_slice * 64;
-            bs = bs_motion(curr, neigh[dir], rpl, rpl);
-            const int i = a - t0[0][dir], tsize = size_q[dir];
-            len_p = len_q = (i == 4 || i == tsize - 4) ? 1 : (i == 8 || i == tsize - 8) ? 2 : 3;
-        }
-        gst<uint8_t>((uint8_t *)F.bs[dir][0] + off, (uint8_t)bs);
-        gst<uint8_t>((uint8_t *)F.max_len_p[dir] + off, (uint8_t)len_p);
-        gst<uint8_t>((uint8_t *)F.max_len_q[dir] + off, (uint8_t)len_q);
-        if (F.n_comp < 3)
-            continue;
-        // ---- chroma tree (:642-754): transform-block edges on the 8-sample chroma grid only
-        int bs_cb = 0, bs_cr = 0;
-        const int grid = (8 << (dir ? F.hs : F.vs)) - 1;
-        if (a == t0[1][dir] && a > 0 && !(a & grid) && !ctb_edge_off && !(fn[dir][2] && fq[2])) {
-            const int joint = fn[dir][5] | fq[5];
-            bs_cb = strong ? 2 : (fn[dir][3] | fq[3] | joint) ? 1 : 0;
-            bs_cr = strong ? 2 : (fn[dir][4] | fq[4] | joint) ? 1 : 0;
-        }
-        gst<uint8_t>((uint8_t *)F.bs[dir][1] + off, (uint8_t)bs_cb);
-        gst<uint8_t>((uint8_t *)F.bs[dir][2] + off, (uint8_t)bs_cr);
-    }
+#define BS_RULES_OUT(tab, v) gst<uint8_t>((uint8_t *)(tab) + off, (uint8_t)(v))
+#include "bs_rules_body.inc"
+#undef BS_RULES_OUT
 }
 
 } // namespace vvc355

@@ -14,48 +14,10 @@
 // MvField table as 768-byte runs.
 #include "common.hpp"
 #include "runtime.hpp"
+#include "rec_map.hpp"
 #include "../../include/vvc_mi355.h"
 
 namespace vvc355 {
-
-static constexpr int kMaxUnits = 32 * 32;          // 128x128 CTU in 4x4 units
-static constexpr uint16_t kNoRec = 0xffff;
-
-// records [first, last) of one kind -> map[unit within the CTU] = record index - first.  `map_tree1` != 0: the records carry a tree bit
-// (flags bit 7) and those of tree 1 go to that map.  Sixteen lanes per record; widths are powers of two in every partitioning a decoder
-// produces (the general case keeps the division).
-template <typename REC>
-__device__ __forceinline__ void map_records(uint16_t *map, uint16_t *map_tree1, uint2 *heads, const REC *recs, int first, int last, int ox, int oy, int lw)
-{
-    const int sub = threadIdx.x & 15;
-    // the records' heads (x0 y0 | w h flags pad: the same 8 bytes for all three record kinds) come in through LDS, 1024 at a time with one
-    // coalesced round trip, so that the painting passes below (sixteen records per pass) do not each wait for a global load
-    for (int c0 = first; c0 < last; c0 += kMaxUnits) {
-        const int nc = min(kMaxUnits, last - c0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < nc; i += 256)
-            heads[i] = gld<uint2>(recs + c0 + i);
-        __syncthreads();
-        for (int k = threadIdx.x >> 4; k < nc; k += 16) {
-            const uint2 head = heads[k];
-            const int r = c0 + k;
-            const int x0 = (int16_t)(head.x & 0xffff), y0 = (int16_t)(head.x >> 16), w = head.y & 0xff, h = (head.y >> 8) & 0xff, flags = (head.y >> 16) & 0xff;
-            uint16_t *m = (map_tree1 && (flags >> 7)) ? map_tree1 : map;
-            const int ux = (x0 - ox) >> 2, uy = (y0 - oy) >> 2, uw = w >> 2, n = uw * (h >> 2);
-            const int base = (uy << lw) + ux;
-            if ((uw & (uw - 1)) == 0) {
-                const int lg = __builtin_ctz(uw | 64);
-                for (int i = sub; i < n; i += 16)
-                    m[base + ((i >> lg) << lw) + (i & (uw - 1))] = (uint16_t)(r - first);
-            } else {
-                for (int i = sub; i < n; i += 16) {
-                    const int dy = i / uw, dx = i - dy * uw;
-                    m[base + (dy << lw) + dx] = (uint16_t)(r - first);
-                }
-            }
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void tabfill_kernel(const vvc355_tab_fill *__restrict__ fp)
 {

@@ -1076,6 +1076,47 @@ typedef struct vvc355_bs_frame {
 
 void vvc355_deblock_bs_pass(void *stream, const vvc355_bs_frame *frame_dev, const vvc355_bs_frame *frame_host);
 
+/*
+ * The same outputs straight from the unit records (bs_rec.hip): the coding-unit and transform-unit side tables above exist only to carry
+ * the 8-byte records of vvc355_tab_fill from one kernel to the next, and with this entry they never reach HBM.  The records are exactly
+ * those vvc355_tab_fill_pass takes (same grouping per CTU, same flag bits, tree bit 7); this pass requires both ctu_first_* arrays.  The
+ * MvField table stays an input and must be filled first (vvc355_tab_fill_pass with n_cu = n_tu = 0 and the motion records does that).
+ * Minimum coding block = 4.  No implicit padding: 208 bytes.
+ *
+ * For a picture whose records cover it every output entry equals what vvc355_tab_fill_pass + vvc355_deblock_bs_pass write, the zeros
+ * included.  Records are NOT trusted: a malformed record (w or h zero or no multiple of 4, x0 or y0 no multiple of 4, a rectangle not inside
+ * its CTU) is skipped.  A unit is complete when it has a coding-unit record, a tree-0 transform-unit record with a coding-unit record at
+ * its origin and, with n_comp == 3, a tree-1 record; if a unit, or its P-side neighbour in a direction (where one exists inside the
+ * picture), is incomplete, the five entries of (unit, direction) are written as 0.  tb_*_c of a unit without a tree-1 record is 0.
+ */
+typedef struct vvc355_bs_rec_frame {
+    uint64_t cu, tu;                          /* DEVICE vvc355_cu_rec[n_cu] / vvc355_tu_rec[n_tu] */
+    uint64_t ctu_first_cu, ctu_first_tu;      /* DEVICE int32[ctb_width * ctb_height + 1] each */
+    uint64_t mvf;                             /* vvc355_mvfield per 4x4 luma unit, row pitch mvf_pitch */
+    uint64_t ref_poc, slice_idx, ctb_to_col_bd, ctb_to_row_bd;      /* as in vvc355_bs_frame */
+    /* outputs, uint8 per 4x4 luma unit, row pitch unit_pitch: same meaning and indexing as in vvc355_bs_frame */
+    uint64_t bs[2][3];
+    uint64_t max_len_p[2], max_len_q[2];
+    uint64_t tb_width_c, tb_height_c;         /* fc->tab.tb_width[CHROMA] / tb_height[CHROMA] in chroma samples (tb_size_c of vvc355_deblock_frame); 0 = not wanted */
+    int32_t  n_cu, n_tu;
+    int32_t  unit_pitch, mvf_pitch;
+    int32_t  width, height, ctb_width, ctb_height;          /* luma picture size; CTUs per row / column */
+    uint8_t  ctb_log2, hs, vs, n_comp;        /* n_comp 1: only the luma outputs are written (and mandatory) */
+    uint8_t  lfase, lfate;
+    uint8_t  pad_[2];
+} vvc355_bs_rec_frame;
+
+/* what vvc355_deblock_bs_rec_pass returns for a frame it refuses: no frame; width or height <= 0 or no multiple of 4; ctb_log2 outside 5..7;
+ * ctb_width / ctb_height not ceil(size >> ctb_log2); unit_pitch or mvf_pitch < width / 4; n_comp not 1 or 3; hs or vs above 1; a negative
+ * count; a record array or its ctu_first_* missing while its count is positive; mvf, ref_poc, slice_idx or a tile map missing; a mandatory
+ * output missing (bs[*][0], max_len_p, max_len_q; with n_comp == 3 also bs[*][1..2]) */
+enum { VVC355_BS_REC_E_FRAME = -1, VVC355_BS_REC_E_SIZE = -2, VVC355_BS_REC_E_CTB = -3, VVC355_BS_REC_E_GRID = -4, VVC355_BS_REC_E_PITCH = -5,
+       VVC355_BS_REC_E_COMP = -6, VVC355_BS_REC_E_SHIFT = -7, VVC355_BS_REC_E_COUNT = -8, VVC355_BS_REC_E_RECORDS = -9,
+       VVC355_BS_REC_E_TABLES = -10, VVC355_BS_REC_E_OUTPUT = -11 };
+/* One launch on `stream`, one workgroup per CTU, no device scratch.  The host copy of the frame is checked before any HIP call.
+ * returns 0, or a negative VVC355_BS_REC_E_* with NOTHING launched */
+int vvc355_deblock_bs_rec_pass(void *stream, const vvc355_bs_rec_frame *frame_dev, const vvc355_bs_rec_frame *frame_host);
+
 /* ------------------------------------------------------------------ SAO stage driver (loopfilter.hip) */
 
 /*
