@@ -160,6 +160,8 @@ BATCH_SIGNATURES = {
     "ts_tb_pass":       ("i", "pppi"),
     # boundary strengths and luma filter lengths straight from the unit records of tab_fill_pass (vvc355_bs_rec_frame): no side tables
     "deblock_bs_rec_pass": ("i", "ppp"),
+    # the QP tables of deblock_frame_pass from the same records and two sidecars of one / two bytes per record (vvc355_qp_rec_frame)
+    "deblock_qp_rec_pass": ("i", "ppp"),
 }
 
 
@@ -680,6 +682,20 @@ class BsRecFrame(ctypes.Structure):
 # what vvc355_deblock_bs_rec_pass returns for a frame it refuses (VVC355_BS_REC_E_*)
 (BS_REC_E_FRAME, BS_REC_E_SIZE, BS_REC_E_CTB, BS_REC_E_GRID, BS_REC_E_PITCH, BS_REC_E_COMP, BS_REC_E_SHIFT, BS_REC_E_COUNT,
  BS_REC_E_RECORDS, BS_REC_E_TABLES, BS_REC_E_OUTPUT) = -1, -2, -3, -4, -5, -6, -7, -8, -9, -10, -11
+
+
+class QpRecFrame(ctypes.Structure):
+    """Mirror of vvc355_qp_rec_frame."""
+    _fields_ = [("cu", ctypes.c_uint64), ("tu", ctypes.c_uint64), ("ctu_first_cu", ctypes.c_uint64), ("ctu_first_tu", ctypes.c_uint64),
+                ("cu_qp", ctypes.c_uint64), ("tu_qp_c", ctypes.c_uint64), ("qp_y", ctypes.c_uint64), ("qp_c", ctypes.c_uint64 * 2),
+                ("n_cu", ctypes.c_int32), ("n_tu", ctypes.c_int32), ("unit_pitch", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ctb_width", ctypes.c_int32), ("ctb_height", ctypes.c_int32),
+                ("ctb_log2", ctypes.c_uint8), ("n_comp", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 2)]
+
+
+# what vvc355_deblock_qp_rec_pass returns for a frame it refuses (VVC355_QP_REC_E_*)
+(QP_REC_E_FRAME, QP_REC_E_SIZE, QP_REC_E_CTB, QP_REC_E_GRID, QP_REC_E_PITCH, QP_REC_E_COMP, QP_REC_E_COUNT, QP_REC_E_RECORDS,
+ QP_REC_E_SIDECAR, QP_REC_E_OUTPUT) = -1, -2, -3, -4, -5, -6, -7, -8, -9, -10
 
 
 class LmcsResidJob(ctypes.Structure):

@@ -49,18 +49,6 @@ __device__ __forceinline__ void paint_halo(uint16_t *halo, uint16_t *halo_tree1,
     }
 }
 
-// CTU rs's range in a record array of n records: [first, last) clamped to the array and to the 65535 records a map entry can name
-__device__ __forceinline__ void ctu_range(const int *firsts, int rs, int n, int &r0, int &r1)
-{
-    r0 = r1 = 0;
-    if (!firsts || n <= 0)
-        return;
-    r0 = min(max(gld<int>(firsts + rs), 0), n);
-    r1 = min(max(gld<int>(firsts + rs + 1), r0), min(n, r0 + 65535));
-}
-
-__device__ __forceinline__ int abs_rec(uint16_t idx, int base) { return idx == kNoRec ? -1 : base + (int)idx; }
-
 // (256, 8): 64 VGPRs, so that the 8 workgroups per CU of an 8K picture (2040 CTUs on 256 CUs) are resident at once
 __global__ __launch_bounds__(256, 8) void bs_rec_kernel(const vvc355_bs_rec_frame *__restrict__ fp)
 {

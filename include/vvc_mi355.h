@@ -1117,6 +1117,48 @@ enum { VVC355_BS_REC_E_FRAME = -1, VVC355_BS_REC_E_SIZE = -2, VVC355_BS_REC_E_CT
  * returns 0, or a negative VVC355_BS_REC_E_* with NOTHING launched */
 int vvc355_deblock_bs_rec_pass(void *stream, const vvc355_bs_rec_frame *frame_dev, const vvc355_bs_rec_frame *frame_host);
 
+/*
+ * The QP tables of vvc355_deblock_frame from the same records (qp_rec.hip): fc->tab.qp[LUMA] as set_qp_y paints it over every coding unit
+ * (set_cb_tab, vvc_ctu.c:144-177) and fc->tab.qp[CB] / [CR] as set_qp_c_tab paints them over every chroma transform block (set_tb_tab,
+ * :179-185, called from set_cu_tabs :1241-1250).  The values travel in two sidecars paired with the records BY INDEX (as vvc355_tb_levels
+ * is paired with the TB records): cu_qp[i] belongs to cu[i], tu_qp_c[i] to tu[i]; the record structs and their pad_ bytes are unchanged.
+ * tu_qp_c is read only for tree-1 records (flags bit 7); the entries of tree-0 records are never looked at.  The bytes are copied, not
+ * interpreted: QpY may be negative, the chroma values carry qp_bd_offset as cu->qp[] does, and for a joint Cb-Cr transform unit with both
+ * flags coded the caller stores cu->qp[JCBCR] in both, as set_qp_c_tab does.
+ *
+ * The outputs plug into vvc355_deblock_frame unchanged: qp_y with min_cb_log2 = 2 and min_cb_width = unit_pitch, qp_c[k] with
+ * min_tu_width = unit_pitch (a coarser MinCbLog2SizeY only means coarser record coordinates).  Every entry with ux < width / 4 and
+ * uy < height / 4 is written in one launch: the value of the record that covers the unit (a coding-unit record for qp_y, a tree-1
+ * transform-unit record for qp_c), or 0 where no record does.  The pitch padding (ux >= width / 4) is not touched.  With n_comp == 1 only
+ * qp_y is written; tu, ctu_first_tu, tu_qp_c and qp_c are not looked at and may be 0.
+ *
+ * Records are NOT trusted, exactly as in vvc355_deblock_bs_rec_pass: a malformed record (w or h zero or no multiple of 4, x0 or y0 no
+ * multiple of 4, a rectangle not inside the CTU it is filed under) paints nothing, a CTU's range in ctu_first_* is clamped to the arrays
+ * and to 65535 records, and the sidecars are read only at indices of records that painted.  No implicit padding: 104 bytes.
+ */
+typedef struct vvc355_qp_rec_frame {
+    uint64_t cu, tu;                      /* DEVICE vvc355_cu_rec[n_cu] / vvc355_tu_rec[n_tu]: the arrays vvc355_deblock_bs_rec_pass takes */
+    uint64_t ctu_first_cu, ctu_first_tu;  /* DEVICE int32[ctb_width * ctb_height + 1] each */
+    uint64_t cu_qp;                       /* DEVICE int8[n_cu]: cu->qp[LUMA] of cu[i] (what set_qp_y leaves in the table) */
+    uint64_t tu_qp_c;                     /* DEVICE int8[n_tu][2]: what set_qp_c_tab paints for the Cb / Cr block of tu[i];
+                                             read only for tree-1 records (flags bit 7); 0 allowed with n_comp == 1 */
+    uint64_t qp_y, qp_c[2];               /* OUTPUTS, int8 per 4x4 luma unit, row pitch unit_pitch */
+    int32_t  n_cu, n_tu, unit_pitch;
+    int32_t  width, height, ctb_width, ctb_height;
+    uint8_t  ctb_log2, n_comp, pad_[2];
+} vvc355_qp_rec_frame;
+
+/* what vvc355_deblock_qp_rec_pass returns for a frame it refuses: no frame; width or height <= 0 or no multiple of 4; ctb_log2 outside 5..7;
+ * ctb_width / ctb_height not ceil(size >> ctb_log2); unit_pitch < width / 4; n_comp not 1 or 3; a negative count; cu or ctu_first_cu missing
+ * while n_cu > 0, or (n_comp == 3) tu or ctu_first_tu missing while n_tu > 0; cu_qp missing while n_cu > 0, or (n_comp == 3) tu_qp_c
+ * missing while n_tu > 0; qp_y missing, or (n_comp == 3) qp_c[0] or qp_c[1] */
+enum { VVC355_QP_REC_E_FRAME = -1, VVC355_QP_REC_E_SIZE = -2, VVC355_QP_REC_E_CTB = -3, VVC355_QP_REC_E_GRID = -4, VVC355_QP_REC_E_PITCH = -5,
+       VVC355_QP_REC_E_COMP = -6, VVC355_QP_REC_E_COUNT = -7, VVC355_QP_REC_E_RECORDS = -8, VVC355_QP_REC_E_SIDECAR = -9,
+       VVC355_QP_REC_E_OUTPUT = -10 };
+/* One launch on `stream`, one workgroup per CTU, no device scratch, no atomics.  The host copy of the frame is checked before any HIP call.
+ * returns 0, or a negative VVC355_QP_REC_E_* with NOTHING launched */
+int vvc355_deblock_qp_rec_pass(void *stream, const vvc355_qp_rec_frame *frame_dev, const vvc355_qp_rec_frame *frame_host);
+
 /* ------------------------------------------------------------------ SAO stage driver (loopfilter.hip) */
 
 /*
