@@ -6,17 +6,18 @@
  * checker / CPU baseline — never as a fallback for the HIP path.
  *
  * Every function restates the reference algorithm from a reading of the cited file:line.
- * PINNED bit-exactly against the reference's own C path (ref_shim.c, `make ref`): the leaf slots of
- * VVCDSPContext and the non-static helpers, on the case lists of tests/ref_cases.py (digests in
- * tests/golden/ref_slots.json) and, where the reference is present, on a wider sweep
+ * PINNED bit-exactly against the reference's own C path (ref_shim.c, ref_shim_intra.c, `make ref`):
+ * the leaf slots of VVCDSPContext and the non-static helpers, the static functions of vvc_intra.c
+ * (dequant, derive_transform_type, ilfnst_transform: orc_dequant, orc_derive_transform_type,
+ * orc_ilfnst_transform) on the case lists of tests/ref_cases.py, and the three slots that take a
+ * populated VVCLocalContext (intra.intra_pred, intra.intra_cclm_pred, intra.lmcs_scale_chroma:
+ * orc_intra_pred_flat, orc_intra_cclm_pred_flat, orc_lmcs_chroma_scale_flat /
+ * orc_lmcs_scale_chroma_flat, behind the host shim's flattening) on those of tests/ref_ctx_cases.py;
+ * digests in tests/golden/ref_slots.json and, where the reference is present, a wider sweep
  * (tests/test_oracle_ref_cpu.py).
  * STILL UNPINNED, cross-checked only by independent properties (tests/test_oracle_cpu.py):
- * the three slots that take a populated VVCLocalContext (intra.intra_pred, intra.intra_cclm_pred,
- * intra.lmcs_scale_chroma: orc_intra_pred_flat, orc_intra_cclm_pred_flat, orc_lmcs_chroma_scale_flat
- * / orc_lmcs_scale_chroma_flat), the static functions of vvc_intra.c (dequant,
- * derive_transform_type, ilfnst_transform: orc_dequant, orc_derive_transform_type,
- * orc_ilfnst_transform) and the caller restatements (orc_bipred_block, orc_gpm_block,
- * orc_affine_block, orc_lmcs_chroma_resid_block, every orc_*_pass and orc_*_frame_build).
+ * the caller restatements (orc_bipred_block, orc_gpm_block, orc_affine_block,
+ * orc_lmcs_chroma_resid_block, every orc_*_pass and orc_*_frame_build).
  *
  * Conventions: `bd` = bit depth (8, 10 or 12); pixels are uint8_t when bd == 8 and uint16_t
  * otherwise; pixel strides are in BYTES exactly as on the reference's function-pointer surface

@@ -1,6 +1,6 @@
 /*
  * oracle/orc_itx.c — CPU restatement of the inverse-transform / residual DSP slots.
- * TEST INFRASTRUCTURE ONLY; slots and 1-D kernels PINNED, orc_dequant UNPINNED (see orc_common.h).
+ * TEST INFRASTRUCTURE ONLY; slots, 1-D kernels and orc_dequant PINNED (see orc_common.h).
  *
  * Follows, by reading:
  *   libavcodec/vvc/vvc_itx_1d.c   (DCT-2 butterflies :88-653 and their nz gating :64-67, matrix_mul :657, LFNST :708)

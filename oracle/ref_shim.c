@@ -6,9 +6,10 @@
  * orc_<slot> signature of vvc_oracle.h (leading `bd`, leading table indices), so the same ctypes table binds the
  * oracle, the product and the reference, plus the non-static helpers the oracle restates.
  *
- * Not covered (they need a populated VVCLocalContext or are static in the reference): intra.intra_pred,
- * intra.intra_cclm_pred, intra.lmcs_scale_chroma, and vvc_intra.c's dequant / derive_transform_type /
- * ilfnst_transform.
+ * The slots that take a populated VVCLocalContext (intra.intra_pred, intra.intra_cclm_pred, intra.lmcs_scale_chroma), the
+ * availability functions and vvc_intra.c's static dequant / derive_transform_type / ilfnst_transform are in ref_shim_intra.c, the
+ * library's second translation unit.  Not covered: the reference's callers (ff_vvc_reconstruct, the inter / filter drivers), which the
+ * oracle restates as block and frame passes.
  */
 #include <stddef.h>
 #include <stdint.h>

@@ -47,6 +47,22 @@ class VVCLocalContext(ctypes.Structure):
                 ("ctb_left_flag", ctypes.c_uint8), ("ctb_up_flag", ctypes.c_uint8), ("end_of_tiles_x", ctypes.c_int), ("lmcs", LmcsCache)]
 
 
+# The DSP table (VVC355DSPContext, member order of the reference's VVCDSPContext, vvcdsp.h:160-168) as an array of pointers:
+# inter 3 * 56 + 11 + sad + 4 dmvr, intra 10, itx 3 + 441 + 1, lmcs 1, lf 6, sao 20, alf 5
+TABLE_POINTERS = 3 * 56 + 16 + 10 + 445 + 1 + 6 + 20 + 5
+INTRA0 = 3 * 56 + 16                         # first pointer of the intra sub-table: intra_cclm_pred, lmcs_scale_chroma, intra_pred, ...
+SAO0 = INTRA0 + 10 + 445 + 1 + 6             # first pointer of the SAO sub-table; edge_restore[2] are its entries 18 and 19
+LC = ctypes.POINTER(VVCLocalContext)
+CCLM_FN = ctypes.CFUNCTYPE(None, LC, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int)
+LMCS_SCALE_FN = ctypes.CFUNCTYPE(None, LC, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int)
+INTRA_PRED_FN = ctypes.CFUNCTYPE(None, LC, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int)
+
+
+def context_slots(tab):
+    """(intra_cclm_pred, lmcs_scale_chroma, intra_pred) of a filled table, callable with a mirror context."""
+    return CCLM_FN(tab[INTRA0 + 0]), LMCS_SCALE_FN(tab[INTRA0 + 1]), INTRA_PRED_FN(tab[INTRA0 + 2])
+
+
 def load_host():
     lib = ctypes.CDLL(os.path.join(ROOT, "ffvvc_amd", "libvvc_mi355_host.so"))
     return lib

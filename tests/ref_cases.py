@@ -14,6 +14,9 @@ Distributions (`DISTS`): uniform random, all-minimum, all-maximum, and a checker
 prediction intermediates the extremes are what `put` can emit at that bit depth (`put_range`), for DMVR planes what `dmvr`
 can emit (`dmvr_max`).  Destinations are pre-filled with a sentinel and compared whole.
 
+The static functions of the reference's vvc_intra.c (dequant, derive_transform_type, ilfnst_transform) are listed here like slots;
+the slots that take the decoder's context have their own case module, tests/ref_ctx_cases.py.
+
 Each builder states its input domain in one line; everything stays inside what the decoder can produce, because the oracle
 is built with -fwrapv and the reference is not: outside the domain a difference is not a finding.
 """
@@ -68,6 +71,8 @@ class Buf:
 
 
 class Case:
+    __slots__ = ("slot", "key", "params", "args", "ret")
+
     def __init__(self, slot, key, params, args, ret=False):
         self.slot, self.key, self.params, self.args, self.ret = slot, key, params, args, ret
 
@@ -722,6 +727,137 @@ def _bdpcm(slot, g):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- vvc_intra.c statics
+
+LEVEL_SCALE = ((40, 45, 51, 57, 64, 72), (57, 64, 72, 80, 90, 102))          # levelScale[][] of 8.7.3
+DQ_QP_LIMIT = 75          # the reference's rem6 / div6 tables end at 75 and it reads past them above: a limit of the reference
+DQ_SENTINEL = 0x5A5A5A          # coefficients outside the scan window: not the scaling process's to touch
+DQ_MATRICES = ("none", "ones", "flat16", "max", "random", "random")
+
+
+def dequant_scale(lw, lh, qp, ts, dep, bd, bits):
+    """(scale, bd_offset) of 8.7.3 for one block.  The generator needs them only to keep the signed product inside 32 bits."""
+    rect = 0 if ts else (lw + lh) & 1
+    q = qp + (1 if dep and not ts else 0)
+    shift = 10 if ts else bd + rect + (lw + lh) // 2 + 10 - bits + dep
+    return LEVEL_SCALE[rect][q % 6] << (q // 6), (1 << shift) >> 1
+
+
+def dequant_factors(lw, lh, win, mat, lm, dc):
+    """Scaling factor m of every position of the window: 16 without a list, else the matrix up-sampled to the block, with the
+    DC value at the origin when the window starts there."""
+    x0, y0, x1, y1 = win
+    if mat is None:
+        return np.full((y1 - y0 + 1, x1 - x0 + 1), 16, np.int64)
+    ys, xs = (np.arange(y0, y1 + 1) << lm) >> lh, (np.arange(x0, x1 + 1) << lm) >> lw
+    m = mat.reshape(1 << lm, 1 << lm)[np.ix_(ys, xs)].astype(np.int64)
+    if dc >= 0 and x0 == 0 and y0 == 0:
+        m[0, 0] = dc
+    return m
+
+
+def dequant_window(g, kind, mw, mh):
+    """Scan window inside mw x mh: 0 the whole of it, 1 one that starts off the origin (in x, in y or in both), 2 a random one at the origin."""
+    if kind == 0:
+        return 0, 0, mw - 1, mh - 1
+    if kind == 2:
+        return 0, 0, g.ints(0, mw), g.ints(0, mh)
+    axis = g.ints(0, 3)
+    x0, y0 = (0 if axis == 1 else g.ints(0, mw)), (0 if axis == 2 else g.ints(0, mh))
+    if x0 == 0 and y0 == 0:
+        x0, y0 = (1, 0) if mw > 1 else (0, 1)
+    return x0, y0, g.ints(x0, mw), g.ints(y0, mh)
+
+
+def _dequant(slot, g):
+    """Domain: every transform block shape 1x2 .. 64x64; scan window within the first 32 columns and rows; qp = tb->qp as derive_qp
+    leaves it, 0 (4 with transform skip) .. 63 + QpBdOffset, and qp + (dep_quant && !ts) <= 75 (DQ_QP_LIMIT); no scaling list with
+    transform skip; the matrix size follows from the block (2x2 for 2-sample blocks, 4x4 for 4-sample ones, else 8x8) and only
+    blocks of 16 samples and more have a DC value; levels in the coefficient range and |level| * scale * m + bd_offset < 2^31 (the
+    reference's product is signed and not built with -fwrapv), drawn up to exactly that bound."""
+    out = []
+    for bd in BDS:
+        for bits in itx_ranges(bd):
+            for lw in range(7):
+                for lh in range(7):
+                    for ts in (0, 1):
+                        for dep in (0, 1):
+                            for k in range(3 if lw + lh else 0):
+                                i = len(out)
+                                addin = 1 if dep and not ts else 0
+                                qp_lo, qp_hi = (4 if ts else 0), min(63 + 6 * (bd - 8), DQ_QP_LIMIT - addin)
+                                qp = (qp_lo, qp_hi, -1, -1)[(i + g.seed) % 4]
+                                qp = g.ints(qp_lo, qp_hi + 1) if qp < 0 else qp
+                                assert qp + addin <= DQ_QP_LIMIT
+                                win = dequant_window(g, g.ints(0, 3) if g.seed else k, min(1 << lw, 32), min(1 << lh, 32))
+                                x0, y0, x1, y1 = win
+                                big = max(lw, lh)
+                                mk = "none" if ts else DQ_MATRICES[g.ints(0, 6)]
+                                lm, mat, dc = 1, None, -1
+                                if mk != "none":
+                                    lm = min(big, 3)
+                                    n = 1 << (2 * lm)
+                                    mat = {"ones": np.full(n, 1), "flat16": np.full(n, 16), "max": np.full(n, 255)}.get(mk)
+                                    mat = (g.ints(1, 256, (n,)) if mat is None else mat).astype(np.uint8)
+                                    if big >= 4:
+                                        dc = (-1, 1, 255, g.ints(1, 256))[g.ints(0, 4)]
+                                scale, offset = dequant_scale(lw, lh, qp, ts, dep, bd, bits)
+                                m = dequant_factors(lw, lh, win, mat, lm, dc)
+                                bound = ((1 << 31) - 1 - offset) // (scale * m)
+                                hi, lo = np.minimum((1 << bits) - 1, bound), -np.minimum(1 << bits, bound)
+                                dist = dist_cycle(i)
+                                unit = field(g, m.shape, 0, 1 << 20, dist, np.int64)
+                                lv = lo + ((unit * (hi - lo)) >> 20)
+                                if dist == "uniform":          # the zero-level skip
+                                    lv = np.where(g.ints(0, 4, m.shape) == 0, 0, lv)
+                                assert int((np.abs(lv) * scale * m + offset).max()) < 1 << 31
+                                c = np.full((1 << lh, 1 << lw), DQ_SENTINEL, np.int32)
+                                c[y0:y1 + 1, x0:x1 + 1] = lv
+                                prm = dict(bd=bd, range=bits, w=1 << lw, h=1 << lh, window=win, qp=qp, ts=ts, dep_quant=dep, matrix=mk, dc=dc, dist=dist)
+                                out.append(Case(slot, (bd, bits), prm,
+                                                [Buf(c), lw, lh, x0, y0, x1, y1, qp, ts, dep, bd, bits, Buf(mat) if mat is not None else 0, lm, dc]))
+    return out
+
+
+TT_SIDES = (1, 2, 4, 8, 16, 32, 64)
+_derive_tt_list = []
+
+
+def _derive_tt(slot, g):
+    """Domain: the whole of it: every tu_flags combination x mts_idx 0..4 x lfnst_idx 0..2 x c_idx 0..2 x w, h in 1..64.  The cases hold
+    only integers, so the list is built once; its `params` are the arguments (flags, mts_idx, lfnst_idx, c_idx, w, h)."""
+    if not _derive_tt_list:
+        for flags in range(256):
+            for mts in range(5):
+                for lfnst in range(3):
+                    for c_idx in range(3):
+                        for w in TT_SIDES:
+                            for h in TT_SIDES:
+                                args = (flags, mts, lfnst, c_idx, w, h)
+                                _derive_tt_list.append(Case(slot, (0,), args, args, ret=True))
+    return _derive_tt_list
+
+
+LFNST_SIDES = (4, 8, 16, 32, 64)
+
+
+def _ilfnst(slot, g):
+    """Domain: blocks of 4..64 a side; sets 1 and 2; every intra mode 0..66 before the wide-angle mapping, handed over mapped for the
+    block's shape (wide_angle, pinned through intra_wide_angle); coefficients in [-2^range, 2^range) over the whole block."""
+    out = []
+    for w in LFNST_SIDES:
+        for h in LFNST_SIDES:
+            for idx in (1, 2):
+                for pre in range(67):
+                    dist = dist_cycle(len(out) + g.seed)
+                    bits = 15 if (len(out) + g.seed) % 5 else 18
+                    c = field(g, (h, w), -(1 << bits), (1 << bits) - 1, dist, np.int32)
+                    mode = wide_angle(pre, w, h)
+                    out.append(Case(slot, (0, idx), dict(w=w, h=h, mode=pre, mapped=mode, lfnst_idx=idx, range=bits, dist=dist),
+                                    [Buf(c), w, h, mode, idx, bits], ret=True))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- intra
 
 INTRA_SIZES = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 16), (16, 4), (8, 32), (32, 8), (64, 16), (16, 64), (4, 64), (64, 4),
@@ -898,6 +1034,7 @@ BUILDERS = {
     "lf_filter_luma": _lf, "lf_filter_chroma": _lf, "lf_ladf_level": _lf,
     "itx": _itx, "inv_lfnst_1d": _lfnst, "add_residual": _residual, "add_residual_joint": _residual,
     "pred_residual_joint": _residual, "transform_bdpcm": _bdpcm,
+    "dequant": _dequant, "derive_transform_type": _derive_tt, "ilfnst_transform": _ilfnst,
     "pred_planar": _intra_simple, "pred_dc": _intra_simple, "pred_v": _intra_simple, "pred_h": _intra_simple,
     "pred_angular_v": _intra_angular, "pred_angular_h": _intra_angular, "pred_mip": _intra_mip,
     "inv_tx_1d": _inv_tx_1d,
@@ -906,9 +1043,9 @@ BUILDERS = {
     "intra_wide_angle": _intra_helpers,
 }
 SLOTS = tuple(BUILDERS)
-EXHAUSTIVE = ("intra_pred_angle", "intra_inv_angle", "intra_nscale", "intra_ref_filter_flag", "intra_mip_size_id")      # whole domain listed: no sweep
+EXHAUSTIVE = ("intra_pred_angle", "intra_inv_angle", "intra_nscale", "intra_ref_filter_flag", "intra_mip_size_id", "derive_transform_type")      # whole domain listed: no sweep
 DEVICE_SLOTS = tuple(s for s in SLOTS if s not in HELPER_SIGNATURES)      # the product exports the DSP slots, not the helpers
-NO_BD_SLOTS = ("sad", "inv_lfnst_1d", "pred_residual_joint", "transform_bdpcm") + tuple(HELPER_SIGNATURES)      # their group keys start with 0
+NO_BD_SLOTS = ("sad", "inv_lfnst_1d", "pred_residual_joint", "transform_bdpcm", "derive_transform_type", "ilfnst_transform") + tuple(HELPER_SIGNATURES)      # their group keys start with 0
 
 
 def slot_bds(slot):
@@ -968,10 +1105,16 @@ def first_difference(case, want, got):
     return None
 
 
+# Slots whose list is too long to digest whole (tests/golden/ref_slots.json is a committed file and the device test replays it): the
+# digests cover every DIGEST_STRIDE-th case.  The stride is a prime that divides no radix of the list's loops, so every value of
+# every argument is met; the whole list is still compared against the live reference (tests/test_oracle_ref_cpu.py).
+DIGEST_STRIDE = {"derive_transform_type": 1009}
+
+
 def groups(slot, seed=0):
     """The case list cut into digest groups: [(group id, [cases])], at most GROUP cases each, grouped by (slot, bit depth, index tuple)."""
     by_key = {}
-    for c in cases(slot, seed):
+    for c in cases(slot, seed)[::DIGEST_STRIDE.get(slot, 1)]:
         by_key.setdefault(c.key, []).append(c)
     out = []
     for key, lst in by_key.items():

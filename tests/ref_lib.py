@@ -7,6 +7,7 @@ import ctypes
 import json
 import os
 import subprocess
+import sys
 
 import ref_cases
 
@@ -21,8 +22,19 @@ def reference_tree():
     return out or None
 
 
+_made = False
+
+
 def load():
-    """The bound reference library, or None when it has not been built."""
+    """The bound reference library, or None when it has not been built.  The first call brings it up to date with its sources
+    (`make ref`, as conftest.load_oracle does for the oracle: a no-op when nothing changed and where there is no reference tree), so
+    that a library left behind by a build of another revision is not mistaken for this one's."""
+    global _made
+    if not _made:
+        _made = True
+        done = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], capture_output=True, text=True)
+        if done.returncode:          # a shim that no longer compiles: say why, the tests then report the library as missing or stale
+            print(f"`make -C oracle ref` failed ({done.returncode}):\n{done.stdout[-2000:]}{done.stderr[-4000:]}", file=sys.stderr)
     if not os.path.exists(LIB_PATH):
         return None
     return ref_cases.bind(ctypes.CDLL(LIB_PATH), "ref_")

@@ -5,10 +5,9 @@ import os
 import pytest
 
 from conftest import ROOT
+from ctx_mirror import INTRA0, SAO0, TABLE_POINTERS          # the table's layout, shared with tests/ref_ctx_cases.py
 
 HOST = os.path.join(ROOT, "ffvvc_amd", "libvvc_mi355_host.so")
-# pointers in the table: inter 3*56 + 11 + sad + 4 dmvr, intra 10, itx 3 + 441 + 1, lmcs 1, lf 6, sao 20, alf 5
-TABLE_POINTERS = 3 * 56 + 16 + 10 + 445 + 1 + 6 + 20 + 5
 
 
 def load():
@@ -63,11 +62,6 @@ def test_context_shim_completes_the_table(bd):
     assert lib.vvc355_dsp_count_slots(buf) == TABLE_POINTERS - (441 - n_itx)
 
 
-# index of the first pointer of each sub-table (member order of VVCDSPContext, vvcdsp.h:160-168)
-INTRA0 = 3 * 56 + 16
-SAO0 = INTRA0 + 10 + 445 + 1 + 6
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("bd", [8, 10])
 def test_context_taking_slots_through_the_table(orc, bd):
@@ -82,10 +76,8 @@ def test_context_taking_slots_through_the_table(orc, bd):
     tab = (ctypes.c_void_p * TABLE_POINTERS)()
     lib.ff_vvc_dsp_init_mi355(tab, bd)
     lib.ff_vvc_dsp_init_mi355_ctx(tab, bd)
-    LC = ctypes.POINTER(cm.VVCLocalContext)
-    cclm_fn = ctypes.CFUNCTYPE(None, LC, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int)(tab[INTRA0 + 0])
-    lmcs_fn = ctypes.CFUNCTYPE(None, LC, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int)(tab[INTRA0 + 1])
-    pred_fn = ctypes.CFUNCTYPE(None, LC, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int)(tab[INTRA0 + 2])
+    LC = cm.LC
+    cclm_fn, lmcs_fn, pred_fn = cm.context_slots(tab)
     restore_fn = [ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ssize_t, ctypes.c_ssize_t, ctypes.POINTER(cm.SAOParams),
                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)(tab[SAO0 + 18 + v])
                   for v in range(2)]

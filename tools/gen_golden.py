@@ -4,7 +4,9 @@ of tests/ref_cases.py.
 
 Needs oracle/_ref/libvvcref.so (`make -C oracle ref`, or __graft_entry__.build() where the reference tree is present).
 For every group of at most 64 cases (slot, bit depth, table indices) the file holds [digest of the concatenated inputs,
-digest of the concatenated outputs]; it holds no samples.  Usage: python tools/gen_golden.py [--check]"""
+digest of the concatenated outputs]; it holds no samples.  A regeneration may only add slots and groups: a recorded digest that
+would change is an error (the case generator drifted, or the reference did), unless --replace says that the change is meant.
+Usage: python tools/gen_golden.py [--check | --replace]"""
 import hashlib
 import json
 import os
@@ -15,6 +17,23 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import ref_cases  # noqa: E402
 import ref_lib    # noqa: E402
+
+try:                  # the tool is also imported by the tests of revisions whose tests/ has no context slots yet
+    import ref_ctx_cases  # noqa: E402
+except ImportError:
+    ref_ctx_cases = None
+
+CONTEXT_SLOTS_AFTER = "ilfnst_transform"          # the context slots follow vvc_intra.c's static functions in the file
+
+
+def slot_order():
+    """[(case module, slot)] in the order of the file.  The last slot stays the last: a slot added anywhere before it shows in
+    `git diff` of the file as added lines only."""
+    order = [(ref_cases, slot) for slot in ref_cases.SLOTS]
+    if ref_ctx_cases is not None:
+        at = [slot for _, slot in order].index(CONTEXT_SLOTS_AFTER) + 1
+        order[at:at] = [(ref_ctx_cases, slot) for slot in ref_ctx_cases.SLOTS]
+    return order
 
 PATH = ref_lib.GOLDEN_PATH
 
@@ -28,13 +47,27 @@ def group_digests(cases, fn):
     return h_in.hexdigest(), h_out.hexdigest()
 
 
+def ctx_group_digests(cases, side):
+    """The same for a group of context cases (tests/ref_ctx_cases.py) run by `side`."""
+    h_in, h_out = hashlib.sha256(), hashlib.sha256()
+    ref_ctx_cases.group_input_digest(h_in, cases)
+    for c in cases:
+        ref_cases.output_digest(h_out, ref_ctx_cases.run(c, side))
+    return h_in.hexdigest(), h_out.hexdigest()
+
+
 def generate(lib, prefix):
     doc = {"source": "reference C path (ff_vvc_dsp_init slots and vvc_intra.c / vvc_itx_1d.c helpers) through oracle/ref_shim.c on tests/ref_cases.py",
            "format": "slots[slot][group] = [sha256 of inputs, sha256 of outputs]; group = bit depth and table indices / chunk of 64 cases",
            "slots": {}}
-    for slot in ref_cases.SLOTS:
-        fn = getattr(lib, prefix + slot)
-        doc["slots"][slot] = {gid.split("/", 1)[1]: list(group_digests(cases, fn)) for gid, cases in ref_cases.groups(slot)}
+    side = None
+    for module, slot in slot_order():
+        if module is ref_cases:
+            fn = getattr(lib, prefix + slot)
+            doc["slots"][slot] = {gid.split("/", 1)[1]: list(group_digests(cases, fn)) for gid, cases in ref_cases.groups(slot)}
+        else:
+            side = side or module.reference_side(lib)
+            doc["slots"][slot] = {gid.split("/", 1)[1]: list(ctx_group_digests(cases, side)) for gid, cases in module.groups(slot)}
     return doc
 
 
@@ -50,6 +83,11 @@ def dumps(doc):
     return "\n".join(lines)
 
 
+def changed_digests(old, new):
+    """Groups of `old` that `new` drops or records differently: [] when `new` only adds to `old`."""
+    return [f"{slot}/{key}" for slot, grp in old.items() for key, rec in grp.items() if new.get(slot, {}).get(key) != rec]
+
+
 def main():
     lib = ref_lib.load()
     if lib is None:
@@ -58,6 +96,10 @@ def main():
     if "--check" in sys.argv:
         with open(PATH) as f:
             sys.exit(0 if f.read() == text else "tests/golden/ref_slots.json is stale")
+    if os.path.exists(PATH) and "--replace" not in sys.argv:
+        bad = changed_digests(ref_lib.load_golden(), json.loads(text)["slots"])
+        if bad:
+            sys.exit(f"{len(bad)} recorded groups would change or vanish (first: {bad[:4]}): nothing written; --replace if that is meant")
     with open(PATH, "w") as f:
         f.write(text)
     n = sum(len(g) for g in json.loads(text)["slots"].values())
