@@ -134,6 +134,9 @@ BATCH_SIGNATURES = {
     "gpm_frame_build":  ("v", "ppp"),
     "gpm_frame_pass":   ("v", "pipp"),
     "gpm_weights":      ("v", "iiiiip"),
+    # the inter half of the CIIP coding units from 32-byte records (vvc355_ciip_cu): job array + RECON command patch, one prediction launch
+    "ciip_frame_build": ("i", "ppp"),
+    "ciip_frame_pass":  ("i", "pipp"),
     "deblock_frame_pass": ("v", "pipp"),
     "sao_frame_pass":   ("v", "pipp"),
     "alf_frame_pass":   ("v", "pippp"),
@@ -379,6 +382,28 @@ class AffineFrame(ctypes.Structure):
 class GpmFrame(ctypes.Structure):
     """Mirror of vvc355_gpm_frame."""
     _fields_ = [("pic", InterFrame), ("cus", ctypes.c_uint64), ("jobs", ctypes.c_uint64), ("n_cus", ctypes.c_int32), ("n_jobs", ctypes.c_int32)]
+
+
+class CiipCu(ctypes.Structure):
+    """Mirror of vvc355_ciip_cu."""
+    _fields_ = [("x0", ctypes.c_int16), ("y0", ctypes.c_int16), ("cb_width", ctypes.c_int16), ("cb_height", ctypes.c_int16),
+                ("hpel_if_idx", ctypes.c_uint8), ("slice", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 2), ("first_job", ctypes.c_uint32),
+                ("scratch_off", ctypes.c_uint32), ("cmd", ctypes.c_uint32 * 3)]
+
+
+class CiipFrame(ctypes.Structure):
+    """Mirror of vvc355_ciip_frame."""
+    _fields_ = [("pic", InterFrame), ("cus", ctypes.c_uint64), ("jobs", ctypes.c_uint64), ("scratch", ctypes.c_uint64), ("cmds", ctypes.c_uint64),
+                ("slice_idx", ctypes.c_uint64), ("ctb_to_col_bd", ctypes.c_uint64), ("ctb_to_row_bd", ctypes.c_uint64),
+                ("n_cus", ctypes.c_int32), ("n_jobs", ctypes.c_int32), ("scratch_len", ctypes.c_int32), ("n_slices", ctypes.c_int32),
+                ("n_cmds", ctypes.c_int32), ("ctb_width", ctypes.c_int32), ("ctb_height", ctypes.c_int32),
+                ("ctb_log2", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 3)]
+
+
+CIIP_NO_CMD = 0xFFFFFFFF             # vvc355_ciip_cu.cmd[c]: the component has no VVC355_RECON_CIIP command
+# what vvc355_ciip_frame_build / _pass return for a frame they refuse (VVC355_CIIP_E_*)
+(CIIP_E_FRAME, CIIP_E_SIZE, CIIP_E_CTB, CIIP_E_GRID, CIIP_E_COUNT, CIIP_E_DEPTH, CIIP_E_FORMAT, CIIP_E_RECORDS, CIIP_E_JOBS,
+ CIIP_E_TABLES, CIIP_E_CMDS) = -1, -2, -3, -4, -5, -6, -7, -8, -9, -10, -11
 
 
 class GpmJob(ctypes.Structure):

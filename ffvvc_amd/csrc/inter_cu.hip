@@ -1,8 +1,9 @@
-// Affine and geometric-partition stage drivers for gfx950: the job arrays of a whole picture's affine and GPM coding units, written
-// on the device from the decoder's MvField table, reference-picture lists and prediction weight tables plus one record per coding
-// unit, then the prediction kernels of affine.hip and mc_fused.hip.  Reference behaviour: predict_inter (libavcodec/vvc/vvc_inter.c:
-// 875-891) -> pred_affine_blk (:828-873, derive_affine_mvc :813-826) and pred_gpm_blk (:466-527); weights derive_weight_uni /
-// derive_weight (:129-177, inter_weight.hpp).
+// Affine, geometric-partition and combined inter / intra (CIIP) stage drivers for gfx950: the job arrays of a whole picture's affine,
+// GPM and CIIP coding units, written on the device from the decoder's MvField table, reference-picture lists and prediction weight
+// tables plus one record per coding unit, then the prediction kernels of affine.hip and mc_fused.hip.  Reference behaviour:
+// predict_inter (libavcodec/vvc/vvc_inter.c:875-891) -> pred_affine_blk (:828-873, derive_affine_mvc :813-826) and pred_gpm_blk
+// (:466-527); the inter part of ff_vvc_predict_ciip (:915; pred_regular_luma :545-581, pred_regular_chroma :583-640,
+// ciip_derive_intra_weight :523-543); weights derive_weight_uni / derive_weight (:129-177, inter_weight.hpp).
 //
 // The GPM weight masks are not the reference's tables but the closed form of the standard's weighted sample prediction for the
 // geometric partitioning mode, evaluated at compile time: one 112x112 mask per angle that a partition uses, indexed at
@@ -26,6 +27,13 @@ static_assert(sizeof(vvc355_affine_frame) == 168 && offsetof(vvc355_affine_frame
 static_assert(sizeof(vvc355_gpm_frame) == 160 && offsetof(vvc355_gpm_frame, cus) == 136 && offsetof(vvc355_gpm_frame, n_cus) == 152,
               "vvc355_gpm_frame layout");
 static_assert(sizeof(vvc355_affine_job) == 96 && sizeof(vvc355_bipred_job) == 104 && sizeof(vvc355_gpm_job) == 120, "job layouts");
+static_assert(sizeof(vvc355_ciip_cu) == 32 && offsetof(vvc355_ciip_cu, first_job) == 12 && offsetof(vvc355_ciip_cu, cmd) == 20, "vvc355_ciip_cu layout");
+static_assert(sizeof(vvc355_ciip_frame) == 224 && offsetof(vvc355_ciip_frame, cus) == 136 && offsetof(vvc355_ciip_frame, n_cus) == 192 &&
+              offsetof(vvc355_ciip_frame, ctb_log2) == 220, "vvc355_ciip_frame layout");
+static_assert(sizeof(vvc355_recon_cmd) == 40 && offsetof(vvc355_recon_cmd, joint) == 33, "vvc355_recon_cmd layout");
+
+// mc_fused.hip: ciip_pred_kernel<bd> over jobs[0 .. n_jobs), one wave per job
+void ciip_pred_launch(hipStream_t stream, int bd, const vvc355_bipred_job *jobs_dev, int n_jobs);
 
 // partition -> angleIdx / distanceIdx and disLut (tables_small.inc; tables.cpp exports the same text as vvc355_tab_gpm_*)
 #define VVC355_TABLE(type, name, count) static constexpr type c_##name[count]
@@ -279,6 +287,148 @@ __global__ __launch_bounds__(256) void gpm_build_kernel(const vvc355_gpm_frame *
     ((vvc355_gpm_job *)F.jobs)[i] = g;
 }
 
+// The inter part of ff_vvc_predict_ciip: one lane per job slot.  A unit's slots are its luma tiles, then its Cb tiles, then its Cr tiles,
+// each in raster order; the lane of a component's first tile also completes that component's VVC355_RECON_CIIP command.  Every slot
+// below n_jobs is written by its own lane and by no other: the job, or zeros (w = h = 0: ciip_pred_kernel skips it) where the slot
+// belongs to a rejected record or to none.  Nothing a record says reaches an address before it is checked against the frame.
+__global__ __launch_bounds__(256) void ciip_build_kernel(const vvc355_ciip_frame *__restrict__ fp)
+{
+    const vvc355_ciip_frame F = load_uniform(fp);
+    const vvc355_inter_frame &f = F.pic;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)F.n_jobs)
+        return;
+    vvc355_bipred_job *slot = (vvc355_bipred_job *)F.jobs + i;
+    vvc355_bipred_job j = {};
+    const vvc355_ciip_cu *cus = (const vvc355_ciip_cu *)F.cus;
+    const int u = find_cu(cus, F.n_cus, i);
+    const vvc355_ciip_cu cu = cus[u];
+    const int x0 = cu.x0, y0 = cu.y0, cbw = cu.cb_width, cbh = cu.cb_height, ctb_log2 = F.ctb_log2;
+    const bool side_ok = cbw >= 4 && cbw <= 64 && !(cbw & (cbw - 1)) && cbh >= 4 && cbh <= 64 && !(cbh & (cbh - 1)) && cbw * cbh >= 64;
+    const bool inside = x0 >= 0 && y0 >= 0 && !((x0 | y0) & 3) && x0 + cbw <= f.width && y0 + cbh <= f.height &&
+                        (x0 >> ctb_log2) == ((x0 + cbw - 1) >> ctb_log2) && (y0 >> ctb_log2) == ((y0 + cbh - 1) >> ctb_log2);
+    // the unit's tiles and its region
+    const bool has_c = f.chroma_format_idc != 0;
+    const int wc = cbw >> f.hs, hc = cbh >> f.vs;
+    const bool blend_c = has_c && wc > 2;                                  // do_ciip (:590)
+    const uint32_t ntl = ((cbw + 15) >> 4) * ((cbh + 15) >> 4), ntc = has_c ? ((wc + 15) >> 4) * ((hc + 15) >> 4) : 0;
+    const uint32_t region = cbw * cbh + (blend_c ? 2 * wc * hc : 0);
+    uint32_t k = i - cu.first_job;
+    if (!side_ok || !inside || i < cu.first_job || cu.slice >= F.n_slices || (uint64_t)cu.first_job + ntl + 2 * ntc > (uint64_t)(uint32_t)F.n_jobs ||
+        (uint64_t)cu.scratch_off + region > (uint64_t)(uint32_t)F.scratch_len || k >= ntl + 2 * ntc) {
+        *slot = j;
+        return;
+    }
+    const MvFieldDev *mvf_tab = (const MvFieldDev *)f.mvf;
+    const MvFieldDev mv = mvf_tab[(y0 >> 2) * f.mvf_stride + (x0 >> 2)];                             // ff_vvc_get_mvf
+    bool mv_ok = mv.pred_flag >= 1 && mv.pred_flag <= 3;
+    for (int l = 0; l < 2; l++)
+        mv_ok = mv_ok && (!(mv.pred_flag & (1 << l)) || (mv.ref_idx[l] >= 0 && mv.ref_idx[l] <= 15));
+    if (!mv_ok) {
+        *slot = j;
+        return;
+    }
+    const vvc355_inter_slice *sl = (const vvc355_inter_slice *)f.slices + cu.slice;
+    const vvc355_ref_pic *refs = (const vvc355_ref_pic *)f.refs;
+    int c = 0;
+    if (k >= ntl) {                                                        // which component's tiles k falls in
+        k -= ntl;
+        c = 1;
+        if (k >= ntc) { k -= ntc; c = 2; }
+    }
+    const int hs = c ? f.hs : 0, vs = c ? f.vs : 0;
+    const int w = cbw >> hs, h = cbh >> vs, tw = min(w, 16), th = min(h, 16);
+    const int ntx = (w + 15) >> 4;
+    const int tx = (k % ntx) * tw, ty = (k / ntx) * th;
+    const int x = (x0 >> hs) + tx, y = (y0 >> vs) + ty;
+    const bool to_plane = c && !blend_c;
+    // component c's part of the unit's region: luma, then Cb, then Cr, rows packed
+    const uint64_t part = F.scratch + (((uint64_t)cu.scratch_off + (c ? cbw * cbh + (c - 1) * wc * hc : 0)) << f.pixel_shift);
+
+    if (to_plane) {                                                       // c is 1 or 2 here; no indexing of the descriptor copy by a variable
+        j.dst_stride = c == 1 ? f.dst_stride[1] : f.dst_stride[2];
+        j.dst = (c == 1 ? f.dst[1] : f.dst[2]) + (uint64_t)y * j.dst_stride + ((uint64_t)x << f.pixel_shift);
+    } else {
+        j.dst = part + ((uint64_t)(ty * w + tx) << f.pixel_shift);
+        j.dst_stride = w << f.pixel_shift;
+    }
+    for (int l = 0; l < 2; l++) {
+        if (!(mv.pred_flag & (1 << l)))
+            continue;
+        const vvc355_ref_pic *rp = refs + l * 16 + mv.ref_idx[l];                                    // pred_get_refs
+        (l ? j.ref1 : j.ref0) = rp->plane[c];
+        (l ? j.ref1_stride : j.ref0_stride) = rp->stride[c];
+        j.mv[2 * l] = mv.mv[l][0];
+        j.mv[2 * l + 1] = mv.mv[l][1];
+    }
+    j.x = (int16_t)x; j.y = (int16_t)y; j.w = (int16_t)tw; j.h = (int16_t)th;
+    j.pic_w = (int16_t)(f.width >> hs); j.pic_h = (int16_t)(f.height >> vs);
+    j.chroma = c > 0; j.hs = f.hs; j.vs = f.vs;
+    j.hf_idx = j.vf_idx = c ? 0 : cu.hpel_if_idx & 1;
+    j.pred_flag = mv.pred_flag;
+    j.lmcs_lut = (!c && sl->lmcs_used) ? f.lmcs_fwd_lut : 0;              // the inter part is mapped before the blend (:573-574)
+    set_pred_weight(j, derive_pred_weight(sl, mv, c, false, true));       // derive_weight(.., dmvr_flag 0) with ciip_flag: no bcw weights (:158)
+    *slot = j;
+
+    if (!F.cmds || k || to_plane)
+        return;
+    // the component's VVC355_RECON_CIIP command: where its inter prediction lies, and ciip_derive_intra_weight (:523-543)
+    const uint32_t ci = cus[u].cmd[c];
+    if (ci >= (uint32_t)F.n_cmds)
+        return;
+    vvc355_recon_cmd *cmd = (vvc355_recon_cmd *)F.cmds + ci;
+    if (cmd->kind != VVC355_RECON_CIIP || cmd->c_idx != c || cmd->x0 != x0 || cmd->y0 != y0 || cmd->w != cbw || cmd->h != cbh)
+        return;
+    // ctb_left / ctb_up: ff_vvc_decode_neighbour (vvc_ctu.c:2468-2495), as the RECON pass derives them
+    const int16_t *slice_idx = (const int16_t *)F.slice_idx, *col_bd = (const int16_t *)F.ctb_to_col_bd, *row_bd = (const int16_t *)F.ctb_to_row_bd;
+    const int rx = x0 >> ctb_log2, ry = y0 >> ctb_log2, ncx = F.ctb_width, rs = ry * ncx + rx, ctb_mask = (1 << ctb_log2) - 1;
+    const bool left_tile = rx > 0 && col_bd[rx] != col_bd[rx - 1];
+    const bool upper_tile = ry > 0 && row_bd[ry] != row_bd[ry - 1];
+    const bool upper_slice = ry > 0 && slice_idx[rs] != slice_idx[rs - ncx];
+    const bool ctb_left = rx > 0 && !left_tile, ctb_up = ry > 0 && !upper_tile && !upper_slice;
+    const bool available_l = ctb_left || (x0 & ctb_mask), available_u = ctb_up || (y0 & ctb_mask);
+    int weight = 1;
+    if (available_u && mvf_tab[((y0 - 1) >> 2) * f.mvf_stride + ((x0 - 1 + cbw) >> 2)].pred_flag == 0)
+        weight++;
+    if (available_l && mvf_tab[((y0 - 1 + cbh) >> 2) * f.mvf_stride + ((x0 - 1) >> 2)].pred_flag == 0)
+        weight++;
+    cmd->resid = part;
+    cmd->joint = (uint8_t)weight;
+}
+
+// the host copy of a CIIP frame, before any HIP call; bd < 0: no bit depth to check (vvc355_ciip_frame_build)
+static int ciip_frame_check(const vvc355_ciip_frame *F, int bd)
+{
+    if (!F)
+        return VVC355_CIIP_E_FRAME;
+    const vvc355_inter_frame &f = F->pic;
+    if (f.width <= 0 || f.height <= 0 || (f.width & 3) || (f.height & 3))
+        return VVC355_CIIP_E_SIZE;
+    if (F->ctb_log2 < 5 || F->ctb_log2 > 7)
+        return VVC355_CIIP_E_CTB;
+    const int ctb = 1 << F->ctb_log2;
+    if (F->ctb_width != (f.width + ctb - 1) >> F->ctb_log2 || F->ctb_height != (f.height + ctb - 1) >> F->ctb_log2)
+        return VVC355_CIIP_E_GRID;
+    if (F->n_cus < 0 || F->n_jobs < 0 || F->scratch_len < 0 || F->n_slices < 0 || F->n_cmds < 0)
+        return VVC355_CIIP_E_COUNT;
+    if (bd >= 0 && ((bd != 8 && bd != 10 && bd != 12) || f.pixel_shift != (bd > 8)))
+        return VVC355_CIIP_E_DEPTH;
+    if (bd < 0 && f.pixel_shift > 1)
+        return VVC355_CIIP_E_DEPTH;
+    const int fmt_hs[4] = { 0, 1, 1, 0 }, fmt_vs[4] = { 0, 1, 0, 0 };
+    if (f.chroma_format_idc > 3 || f.hs != fmt_hs[f.chroma_format_idc] || f.vs != fmt_vs[f.chroma_format_idc])
+        return VVC355_CIIP_E_FORMAT;
+    if (F->n_cus > 0 && !F->cus)
+        return VVC355_CIIP_E_RECORDS;
+    if (F->n_jobs > 0 && !F->jobs)
+        return VVC355_CIIP_E_JOBS;
+    if (!F->scratch || !f.mvf || !f.refs || !f.slices || !f.dst[0] || (f.chroma_format_idc && (!f.dst[1] || !f.dst[2])) || f.mvf_stride < f.width / 4)
+        return VVC355_CIIP_E_TABLES;
+    if (F->cmds && (!F->slice_idx || !F->ctb_to_col_bd || !F->ctb_to_row_bd))
+        return VVC355_CIIP_E_CMDS;
+    return 0;
+}
+
 } // namespace vvc355
 
 extern "C" {
@@ -312,6 +462,28 @@ void vvc355_gpm_frame_pass(void *stream, int bd, const vvc355_gpm_frame *frame_d
     if (frame_host->n_cus <= 0 || frame_host->n_jobs <= 0) return;
     vvc355_gpm_frame_build(stream, frame_dev, frame_host);
     vvc355_gpm_batch(stream, bd, (const vvc355_gpm_job *)frame_host->jobs, frame_host->n_jobs);
+}
+
+int vvc355_ciip_frame_build(void *stream, const vvc355_ciip_frame *frame_dev, const vvc355_ciip_frame *frame_host)
+{
+    const int err = frame_dev ? vvc355::ciip_frame_check(frame_host, -1) : VVC355_CIIP_E_FRAME;
+    if (err)
+        return err;
+    if (frame_host->n_cus == 0 || frame_host->n_jobs == 0) return 0;
+    hipLaunchKernelGGL(vvc355::ciip_build_kernel, dim3((frame_host->n_jobs + 255) / 256), dim3(256), 0, (hipStream_t)stream, frame_dev);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int vvc355_ciip_frame_pass(void *stream, int bd, const vvc355_ciip_frame *frame_dev, const vvc355_ciip_frame *frame_host)
+{
+    const int err = frame_dev ? vvc355::ciip_frame_check(frame_host, bd) : VVC355_CIIP_E_FRAME;
+    if (err)
+        return err;
+    if (frame_host->n_cus == 0 || frame_host->n_jobs == 0) return 0;
+    vvc355_ciip_frame_build(stream, frame_dev, frame_host);
+    vvc355::ciip_pred_launch((hipStream_t)stream, bd, (const vvc355_bipred_job *)frame_host->jobs, frame_host->n_jobs);
+    return 0;
 }
 
 void vvc355_gpm_weights(int partition_idx, int cb_width, int cb_height, int hs, int vs, uint8_t *out)

@@ -645,6 +645,23 @@ __global__ __launch_bounds__(256) void bipred_chroma_pair_kernel(const vvc355_bi
     }
 }
 
+// The inter half of combined inter / intra coding units (vvc355_ciip_frame_pass): one wave per job, luma and chroma tiles of a
+// picture in one launch.  CIIP has neither DMVR nor BDOF, so every job takes bipred_plain and a wave needs only the plain path's
+// LDS.  A job with w == 0 or h == 0 does nothing: the builder leaves such jobs in the slots of the records it rejects.
+template <int BD>
+__global__ __launch_bounds__(256) void ciip_pred_kernel(const vvc355_bipred_job *__restrict__ jobs, int n_jobs)
+{
+    __shared__ __attribute__((aligned(16))) BipredLds lds_all[4];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int ji = xcd_chunked(blockIdx.x, gridDim.x) * 4 + wave;
+    if (ji >= n_jobs)
+        return;
+    const vvc355_bipred_job job = load_uniform(jobs + ji);
+    if (job.w <= 0 || job.h <= 0)                     // wave-uniform
+        return;
+    bipred_plain<BD>(&job, lds_all[wave], lane);
+}
+
 } // namespace vvc355
 
 extern "C" void vvc355_pred_fused_batch(void *stream, int bd, const vvc355_pred_job *jobs_dev, int n_jobs)
@@ -680,3 +697,14 @@ extern "C" void vvc355_bipred_chroma_batch(void *stream, int bd, const vvc355_bi
     HIP_CHECK(hipGetLastError());
 }
 
+// the launch of ciip_pred_kernel for inter_cu.hip's vvc355_ciip_frame_pass (the kernel lives here, next to bipred_plain)
+namespace vvc355 {
+
+void ciip_pred_launch(hipStream_t stream, int bd, const vvc355_bipred_job *jobs_dev, int n_jobs)
+{
+    if (n_jobs <= 0) return;
+    VVC355_BD_DISPATCH(bd, hipLaunchKernelGGL((ciip_pred_kernel<BD>), dim3((n_jobs + 3) / 4), dim3(256), 0, stream, jobs_dev, n_jobs));
+    HIP_CHECK(hipGetLastError());
+}
+
+} // namespace vvc355

@@ -934,6 +934,79 @@ void vvc355_gpm_frame_pass(void *stream, int bd, const vvc355_gpm_frame *frame_d
  * builder writes read for a component of a coding unit of this partition and size: the same masks and the same addressing */
 void vvc355_gpm_weights(int partition_idx, int cb_width, int cb_height, int hs, int vs, uint8_t *out);
 
+/*
+ * The inter half of the combined inter / intra (CIIP) coding units of a whole picture (cu->ciip_flag; ff_vvc_predict_ciip,
+ * vvc_inter.c:915), the fourth kind of inter coding unit: a regular merge unit with num_sb_x = num_sb_y = 1 and neither DMVR nor BDOF,
+ * whose inter prediction is not the picture's but one operand of inter.put_ciip.  From the decoder's tables and one 32-byte record per
+ * unit the builder writes, per unit, the vvc355_bipred_job of its luma tiles, then of its Cb tiles, then of its Cr tiles (<= 16x16 in the
+ * component's own samples, row-major): motion, ref_idx, bcw_idx and pred_flag from the MvField entry at (x0, y0), filter set
+ * hpel_if_idx on luma and 0 on chroma, rec = 0, dmvr = bdof = 0, weights of derive_weight_uni / derive_weight with ciip_flag set (bcw
+ * weights are ignored, :158; explicit weighted prediction applies).
+ *   luma             dst = the unit's region of `scratch` (cb_width x cb_height pixels, packed rows), stored through pic.lmcs_fwd_lut where
+ *                    the slice has lmcs_used: the inter part of a CIIP block is mapped before the blend (:573-574)
+ *   chroma, wc > 2   (wc = cb_width >> hs, hc = cb_height >> vs) likewise: Cb at scratch_off + cb_width * cb_height, Cr wc * hc further
+ *   chroma, wc <= 2  the reference does not blend (do_ciip, :590): the inter prediction IS the chroma, dst = the picture plane; the
+ *                    unit's region is luma only and cmd[1], cmd[2] are ignored
+ * With cmds != 0 the builder also completes the unit's VVC355_RECON_CIIP commands (declared with the RECON stage driver below), which a
+ * decoder can then upload with resid = 0 and joint = 0: cmds[cmd[c]].resid = the DEVICE address of component c's region and .joint = the
+ * intra weight of ciip_derive_intra_weight (:523-543), 1 + (upper neighbour available and intra) + (left neighbour available and intra)
+ * from the MvField entries at ((x0 + cb_width - 1) >> 2, (y0 - 1) >> 2) and ((x0 - 1) >> 2, (y0 + cb_height - 1) >> 2), available = not on
+ * the CTU's edge, or ctb_up / ctb_left of ff_vvc_decode_neighbour (vvc_ctu.c:2468: the upper CTU exists in the same tile and slice; the
+ * left CTU exists in the same tile).  A command is patched only when cmd[c] < n_cmds, its kind is VVC355_RECON_CIIP and its c_idx, x0, y0,
+ * w, h are the record's; no other byte of the command array changes.
+ *
+ * pic is used as the affine / GPM drivers use it: dst, dst_stride, mvf, mvf_stride, refs, slices, width, height, hs, vs,
+ * chroma_format_idc, pixel_shift and lmcs_fwd_lut are read; pus, jobs_luma, jobs_chroma, records, dmvr_mvf, n_pus and n_jobs are ignored.
+ * CIIP units must not also be listed in pus[] of vvc355_inter_frame_pass (that pass would predict them onto the picture).
+ *
+ * Records are NOT trusted with anything that decides an address.  A unit is rejected when x0 or y0 is no multiple of 4; a side is not one
+ * of 4, 8, 16, 32, 64 or the area is below 64; the rectangle is not inside the picture and one CTU; slice >= n_slices; first_job + the
+ * unit's tiles > n_jobs; its region is not inside [0, scratch_len); the MvField entry's pred_flag is 0 or above 3; a used list's ref_idx
+ * is outside 0..15.  A rejected unit's job slots get w = h = 0 (the prediction kernel skips those), nothing of it is written to scratch
+ * or planes and none of its commands is patched.  Every one of the n_jobs slots is written by the builder: slots no record claims are
+ * zeroed.  first_job must not decrease along cus[]; regions of different units that overlap are the caller's contract, not checked.
+ * No implicit padding: vvc355_ciip_cu 32 bytes, vvc355_ciip_frame 224 bytes.
+ */
+typedef struct vvc355_ciip_cu {
+    int16_t  x0, y0, cb_width, cb_height;     /* luma samples; 4 .. 64 per side, cb_width * cb_height >= 64 */
+    uint8_t  hpel_if_idx;                     /* pu->mi.hpel_if_idx (bit 0 is read) */
+    uint8_t  slice;                           /* index into pic.slices[] */
+    uint8_t  pad_[2];
+    uint32_t first_job;                       /* running sum of the units' tiles: ceil(w / 16) * ceil(h / 16) per present component */
+    uint32_t scratch_off;                     /* PIXEL offset of the unit's region in frame.scratch: luma, then (wc > 2) Cb, then Cr */
+    uint32_t cmd[3];                          /* indices of the unit's Y / Cb / Cr VVC355_RECON_CIIP commands in frame.cmds; 0xFFFFFFFF = none */
+} vvc355_ciip_cu;
+typedef struct vvc355_ciip_frame {
+    vvc355_inter_frame pic;       /* the picture (see above) */
+    uint64_t cus;                 /* DEVICE vvc355_ciip_cu[n_cus] */
+    uint64_t jobs;                /* DEVICE scratch, vvc355_bipred_job[n_jobs] */
+    uint64_t scratch;             /* DEVICE pixels (pic.pixel_shift), scratch_len of them: the units' inter predictions */
+    uint64_t cmds;                /* DEVICE vvc355_recon_cmd[n_cmds], read-write; 0 = prediction only, no command is read or patched */
+    uint64_t slice_idx, ctb_to_col_bd, ctb_to_row_bd;    /* as in vvc355_recon_frame; read only with cmds != 0 */
+    int32_t  n_cus, n_jobs;
+    int32_t  scratch_len;         /* pixels */
+    int32_t  n_slices, n_cmds;
+    int32_t  ctb_width, ctb_height;
+    uint8_t  ctb_log2;
+    uint8_t  pad_[3];
+} vvc355_ciip_frame;
+
+/* what the two entries return for a frame they refuse: no frame; width or height <= 0 or no multiple of 4; ctb_log2 outside 5..7;
+ * ctb_width / ctb_height not ceil(size >> ctb_log2); a negative count (n_cus, n_jobs, scratch_len, n_slices, n_cmds); (_pass) bd not 8, 10
+ * or 12, or pixel_shift != (bd > 8); chroma_format_idc above 3, hs or vs above 1 or not the format's (0: 0 0, 1: 1 1, 2: 1 0, 3: 0 0);
+ * cus missing while n_cus > 0; jobs missing while n_jobs > 0; scratch, mvf, refs, slices or a dst plane of a present component missing,
+ * or mvf_stride < width / 4; slice_idx or a tile map missing while cmds is set */
+enum { VVC355_CIIP_E_FRAME = -1, VVC355_CIIP_E_SIZE = -2, VVC355_CIIP_E_CTB = -3, VVC355_CIIP_E_GRID = -4, VVC355_CIIP_E_COUNT = -5,
+       VVC355_CIIP_E_DEPTH = -6, VVC355_CIIP_E_FORMAT = -7, VVC355_CIIP_E_RECORDS = -8, VVC355_CIIP_E_JOBS = -9, VVC355_CIIP_E_TABLES = -10,
+       VVC355_CIIP_E_CMDS = -11 };
+/* The host copy of the frame is checked before any HIP call: both return 0, or a negative VVC355_CIIP_E_* with NOTHING launched.
+ * n_cus == 0 returns 0 and launches nothing.  Both kernels read their descriptors through device addresses: the sequence can be
+ * captured with vvc355_graph_begin / _end. */
+/* job array + command patch only */
+int vvc355_ciip_frame_build(void *stream, const vvc355_ciip_frame *frame_dev, const vvc355_ciip_frame *frame_host);
+/* build, then ONE prediction launch over jobs[0 .. n_jobs), luma and chroma tiles together */
+int vvc355_ciip_frame_pass(void *stream, int bd, const vvc355_ciip_frame *frame_dev, const vvc355_ciip_frame *frame_host);
+
 /* ------------------------------------------------------------------ affine sub-blocks with PROF (affine.hip) */
 
 /*
