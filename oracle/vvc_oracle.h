@@ -1,6 +1,6 @@
 /*
  * oracle/vvc_oracle.h — C API of the CPU oracle (TEST INFRASTRUCTURE ONLY; leaf slots and helpers
- * pinned against the reference, callers and context-taking slots unpinned: see orc_common.h).  One function per slot of the reference's VVCDSPContext
+ * pinned against the reference: see orc_common.h for what is and what is not).  One function per slot of the reference's VVCDSPContext
  * (libavcodec/vvc/vvcdsp.h:48-168): same argument order and meaning, with the bit depth the
  * reference selects at ff_vvc_dsp_init() time (vvcdsp.c:228) passed as a leading `bd` argument,
  * and table indices (luma/chroma, frac/int, h/v) passed as leading ints.

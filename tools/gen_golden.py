@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/ref_slots.json: SHA-256 digests of what the reference's own C path computes on the case lists
-of tests/ref_cases.py.
+"""Regenerate tests/golden/ref_slots.json and tests/golden/ref_passes.json: SHA-256 digests of what the reference's own C path computes
+on the case lists of tests/ref_cases.py, and of what its in-loop filter callers compute on the pictures of tests/ref_pass_cases.py.
 
 Needs oracle/_ref/libvvcref.so (`make -C oracle ref`, or __graft_entry__.build() where the reference tree is present).
 For every group of at most 64 cases (slot, bit depth, table indices) the file holds [digest of the concatenated inputs,
 digest of the concatenated outputs]; it holds no samples.  A regeneration may only add slots and groups: a recorded digest that
 would change is an error (the case generator drifted, or the reference did), unless --replace says that the change is meant.
+ref_passes.json holds per picture one digest of the inputs, one per output table and one per plane after each stage, under the same rule.
 Usage: python tools/gen_golden.py [--check | --replace]"""
 import hashlib
 import json
@@ -22,6 +23,11 @@ try:                  # the tool is also imported by the tests of revisions whos
     import ref_ctx_cases  # noqa: E402
 except ImportError:
     ref_ctx_cases = None
+
+try:                  # ... or no whole-picture passes yet (ref_passes.json is then left alone)
+    import ref_pass_cases  # noqa: E402
+except ImportError:
+    ref_pass_cases = None
 
 CONTEXT_SLOTS_AFTER = "ilfnst_transform"          # the context slots follow vvc_intra.c's static functions in the file
 
@@ -83,6 +89,27 @@ def dumps(doc):
     return "\n".join(lines)
 
 
+def generate_passes(lib, orc):
+    """The document of ref_passes.json: the reference's whole-picture runs (oracle/ref_shim_filter.c).  `orc` only builds the pictures that
+    bs_rec_cases caches together with the oracle's tables; nothing of the oracle's enters the file."""
+    return {"source": "reference in-loop filter callers (ff_vvc_deblock_vertical / _horizontal, ff_vvc_sao_filter, ff_vvc_alf_filter) through "
+                      "oracle/ref_shim_filter.c on tests/ref_pass_cases.py",
+            "format": "pictures[name][key] = sha256: inputs; the ten bS / filter-length tables; the planes after each stage (v, h, sao, alf + component)",
+            "pictures": {name: ref_pass_cases.host_digests(orc, lib, "ref", name) for name in ref_pass_cases.picture_names()}}
+
+
+def dumps_passes(doc):
+    lines = ["{", f' "source": {json.dumps(doc["source"])},', f' "format": {json.dumps(doc["format"])},', ' "pictures": {']
+    pics = list(doc["pictures"].items())
+    for i, (name, rec) in enumerate(pics):
+        lines.append(f"  {json.dumps(name)}: {{")
+        items = list(rec.items())
+        lines += [f"   {json.dumps(k)}: {json.dumps(v)}" + ("," if j + 1 < len(items) else "") for j, (k, v) in enumerate(items)]
+        lines.append("  }" + ("," if i + 1 < len(pics) else ""))
+    lines += [" }", "}", ""]
+    return "\n".join(lines)
+
+
 def changed_digests(old, new):
     """Groups of `old` that `new` drops or records differently: [] when `new` only adds to `old`."""
     return [f"{slot}/{key}" for slot, grp in old.items() for key, rec in grp.items() if new.get(slot, {}).get(key) != rec]
@@ -93,17 +120,26 @@ def main():
     if lib is None:
         sys.exit(f"{ref_lib.LIB_PATH} is missing: run `make -C oracle ref` where the reference tree is present")
     text = dumps(generate(lib, "ref_"))
+    passes = dumps_passes(generate_passes(lib, ref_lib.load_oracle()))
+    p_path = ref_pass_cases.GOLDEN_PATH
     if "--check" in sys.argv:
         with open(PATH) as f:
-            sys.exit(0 if f.read() == text else "tests/golden/ref_slots.json is stale")
-    if os.path.exists(PATH) and "--replace" not in sys.argv:
-        bad = changed_digests(ref_lib.load_golden(), json.loads(text)["slots"])
+            if f.read() != text:
+                sys.exit("tests/golden/ref_slots.json is stale")
+        with open(p_path) as f:
+            sys.exit(0 if f.read() == passes else "tests/golden/ref_passes.json is stale")
+    if "--replace" not in sys.argv:
+        bad = changed_digests(ref_lib.load_golden(), json.loads(text)["slots"]) if os.path.exists(PATH) else []
+        bad += changed_digests(ref_pass_cases.load_golden(), json.loads(passes)["pictures"]) if os.path.exists(p_path) else []
         if bad:
             sys.exit(f"{len(bad)} recorded groups would change or vanish (first: {bad[:4]}): nothing written; --replace if that is meant")
     with open(PATH, "w") as f:
         f.write(text)
     n = sum(len(g) for g in json.loads(text)["slots"].values())
     print(f"wrote {PATH}: {n} groups, {len(text)} bytes")
+    with open(p_path, "w") as f:
+        f.write(passes)
+    print(f"wrote {p_path}: {len(json.loads(passes)['pictures'])} pictures, {len(passes)} bytes")
 
 
 if __name__ == "__main__":
