@@ -97,6 +97,11 @@ RUNTIME_SIGNATURES = {
     "graph_end":      ("p", "p"),
     "graph_launch":   ("v", "pp"),
     "graph_destroy":  ("v", "p"),
+    "event_create":   ("p", ""),
+    "event_destroy":  ("v", "p"),
+    "event_record":   ("v", "pp"),
+    "stream_wait_event": ("v", "pp"),
+    "event_query":    ("i", "p"),
     "version":        ("p", ""),
     "set_error_policy": ("v", "i"),
     "last_error":     ("i", ""),
@@ -128,14 +133,18 @@ BATCH_SIGNATURES = {
     "affine_batch":     ("v", "pipi"),
     "gpm_batch":        ("v", "pipi"),
     "inter_frame_build": ("v", "ppp"),
+    "inter_frame_predict": ("v", "pipp"),
     "inter_frame_pass": ("v", "pipp"),
     "affine_frame_build": ("v", "ppp"),
+    "affine_frame_predict": ("v", "pipp"),
     "affine_frame_pass": ("v", "pipp"),
     "gpm_frame_build":  ("v", "ppp"),
+    "gpm_frame_predict": ("v", "pipp"),
     "gpm_frame_pass":   ("v", "pipp"),
     "gpm_weights":      ("v", "iiiiip"),
     # the inter half of the CIIP coding units from 32-byte records (vvc355_ciip_cu): job array + RECON command patch, one prediction launch
     "ciip_frame_build": ("i", "ppp"),
+    "ciip_frame_predict": ("i", "pipp"),
     "ciip_frame_pass":  ("i", "pipp"),
     "deblock_frame_pass": ("v", "pipp"),
     "sao_frame_pass":   ("v", "pipp"),
@@ -165,6 +174,12 @@ BATCH_SIGNATURES = {
     "deblock_bs_rec_pass": ("i", "ppp"),
     # the QP tables of deblock_frame_pass from the same records and two sidecars of one / two bytes per record (vvc355_qp_rec_frame)
     "deblock_qp_rec_pass": ("i", "ppp"),
+    # inverse luma mapping of a whole picture from the per-CTB slice index and the per-slice flags (vvc355_lmcs_frame): no job array
+    "lmcs_frame_pass":  ("i", "pipp"),
+    # is a ticket order one recon_frame_pass can run?  (host only)
+    "recon_order_check": ("i", "piipi"),
+    # every record-path stage of a picture in the documented order, validated as a whole before the first launch (vvc355_picture, HOST memory)
+    "picture_pass":     ("i", "pip"),
 }
 
 
@@ -721,6 +736,56 @@ class QpRecFrame(ctypes.Structure):
 # what vvc355_deblock_qp_rec_pass returns for a frame it refuses (VVC355_QP_REC_E_*)
 (QP_REC_E_FRAME, QP_REC_E_SIZE, QP_REC_E_CTB, QP_REC_E_GRID, QP_REC_E_PITCH, QP_REC_E_COMP, QP_REC_E_COUNT, QP_REC_E_RECORDS,
  QP_REC_E_SIDECAR, QP_REC_E_OUTPUT) = -1, -2, -3, -4, -5, -6, -7, -8, -9, -10
+
+
+class LmcsFrame(ctypes.Structure):
+    """Mirror of vvc355_lmcs_frame."""
+    _fields_ = [("plane", ctypes.c_uint64), ("inv_lut", ctypes.c_uint64), ("slice_idx", ctypes.c_uint64), ("slice_lmcs_used", ctypes.c_uint64),
+                ("stride", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ctb_width", ctypes.c_int32),
+                ("ctb_height", ctypes.c_int32), ("n_slices", ctypes.c_int32), ("ctb_log2", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 3)]
+
+
+# what vvc355_lmcs_frame_pass returns for a frame it refuses (VVC355_LMCS_FRAME_E_*)
+(LMCS_FRAME_E_FRAME, LMCS_FRAME_E_BD, LMCS_FRAME_E_SIZE, LMCS_FRAME_E_CTB, LMCS_FRAME_E_GRID, LMCS_FRAME_E_STRIDE, LMCS_FRAME_E_COUNT,
+ LMCS_FRAME_E_TABLES) = -1, -2, -3, -4, -5, -6, -7, -8
+
+# what vvc355_recon_order_check returns for an order it refuses (VVC355_RECON_ORDER_E_*)
+(RECON_ORDER_E_ARGS, RECON_ORDER_E_RANGE, RECON_ORDER_E_EMPTY, RECON_ORDER_E_DUPLICATE, RECON_ORDER_E_MISSING,
+ RECON_ORDER_E_DEPENDENCY) = -1, -2, -3, -4, -5, -6
+
+
+class StageRef(ctypes.Structure):
+    """Mirror of vvc355_stage_ref: (DEVICE address, HOST address) of a stage's frame descriptor; host == 0 skips the stage."""
+    _fields_ = [("dev", ctypes.c_uint64), ("host", ctypes.c_uint64)]
+
+
+PIC_STAGES = ("tab_fill", "inter", "affine", "gpm", "ciip", "intra_tb", "bs_rec", "qp_rec", "alf", "inter_tb", "ts_tb", "lmcs_scale",
+              "recon", "lmcs", "deblock_v", "deblock_h", "sao")
+
+
+class Picture(ctypes.Structure):
+    """Mirror of vvc355_picture (HOST memory)."""
+    _fields_ = [(n, StageRef) for n in PIC_STAGES] + [
+        ("alf_work", ctypes.c_uint64), ("recon_ctus_host", ctypes.c_uint64), ("recon_order_host", ctypes.c_uint64),
+        ("refs", ctypes.c_uint64 * 32), ("done", ctypes.c_uint64), ("n_refs", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+# VVC355_PIC_STAGE_*: which stage refused the picture
+(PIC_STAGE_PICTURE, PIC_STAGE_TAB_FILL, PIC_STAGE_INTER, PIC_STAGE_AFFINE, PIC_STAGE_GPM, PIC_STAGE_CIIP, PIC_STAGE_INTRA_TB,
+ PIC_STAGE_BS_REC, PIC_STAGE_QP_REC, PIC_STAGE_ALF, PIC_STAGE_INTER_TB, PIC_STAGE_TS_TB, PIC_STAGE_LMCS_SCALE, PIC_STAGE_RECON,
+ PIC_STAGE_RECON_ORDER, PIC_STAGE_LMCS, PIC_STAGE_DEBLOCK_V, PIC_STAGE_DEBLOCK_H, PIC_STAGE_SAO) = range(1, 20)
+# codes of PIC_STAGE_PICTURE (VVC355_PIC_E_*)
+PIC_E_NO_DEVICE_FRAME, PIC_E_PICTURE, PIC_E_CIIP_CMDS, PIC_E_SCALE_TABLE, PIC_E_REFS, PIC_E_CAPTURE = -1, -2, -3, -4, -5, -6
+
+
+def pic_stage(ret: int) -> int:
+    """VVC355_PIC_STAGE(ret)."""
+    return (-ret) >> 8
+
+
+def pic_code(ret: int) -> int:
+    """VVC355_PIC_CODE(ret)."""
+    return -((-ret) & 255)
 
 
 class LmcsResidJob(ctypes.Structure):

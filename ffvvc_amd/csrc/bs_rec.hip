@@ -24,6 +24,7 @@
 #include "rec_map.hpp"
 #include "bs_rules.hpp"
 #include "../../include/vvc_mi355.h"
+#include "stage_checks.hpp"
 
 namespace vvc355 {
 
@@ -200,7 +201,7 @@ __global__ __launch_bounds__(256, 8) void bs_rec_kernel(const vvc355_bs_rec_fram
 } // namespace vvc355
 
 // the frame as the header states it: every refusal before any HIP call
-static int bs_rec_check(const vvc355_bs_rec_frame *f)
+int vvc355::bs_rec_check(const vvc355_bs_rec_frame *f)
 {
     if (!f)
         return VVC355_BS_REC_E_FRAME;
@@ -234,7 +235,7 @@ static int bs_rec_check(const vvc355_bs_rec_frame *f)
 
 extern "C" int vvc355_deblock_bs_rec_pass(void *stream, const vvc355_bs_rec_frame *frame_dev, const vvc355_bs_rec_frame *frame_host)
 {
-    const int err = frame_dev ? bs_rec_check(frame_host) : VVC355_BS_REC_E_FRAME;
+    const int err = frame_dev ? vvc355::bs_rec_check(frame_host) : VVC355_BS_REC_E_FRAME;
     if (err)
         return err;
     hipLaunchKernelGGL(vvc355::bs_rec_kernel, dim3(frame_host->ctb_width * frame_host->ctb_height), dim3(256), 0, (hipStream_t)stream, frame_dev);

@@ -14,6 +14,7 @@
 #include "inter_weight.hpp"
 #include "runtime.hpp"
 #include "../../include/vvc_mi355.h"
+#include "stage_checks.hpp"
 
 namespace vvc355 {
 
@@ -397,7 +398,7 @@ __global__ __launch_bounds__(256) void ciip_build_kernel(const vvc355_ciip_frame
 }
 
 // the host copy of a CIIP frame, before any HIP call; bd < 0: no bit depth to check (vvc355_ciip_frame_build)
-static int ciip_frame_check(const vvc355_ciip_frame *F, int bd)
+int ciip_frame_check(const vvc355_ciip_frame *F, int bd)
 {
     if (!F)
         return VVC355_CIIP_E_FRAME;
@@ -444,6 +445,12 @@ void vvc355_affine_frame_pass(void *stream, int bd, const vvc355_affine_frame *f
 {
     if (frame_host->n_cus <= 0 || frame_host->n_jobs <= 0) return;
     vvc355_affine_frame_build(stream, frame_dev, frame_host);
+    vvc355_affine_frame_predict(stream, bd, frame_dev, frame_host);
+}
+
+void vvc355_affine_frame_predict(void *stream, int bd, const vvc355_affine_frame *, const vvc355_affine_frame *frame_host)
+{
+    if (frame_host->n_cus <= 0 || frame_host->n_jobs <= 0) return;
     vvc355_affine_batch(stream, bd, (const vvc355_affine_job *)frame_host->jobs_luma, frame_host->n_jobs);
     if (frame_host->pic.chroma_format_idc)
         vvc355_bipred_chroma_batch(stream, bd, (const vvc355_bipred_job *)frame_host->jobs_chroma,
@@ -461,6 +468,12 @@ void vvc355_gpm_frame_pass(void *stream, int bd, const vvc355_gpm_frame *frame_d
 {
     if (frame_host->n_cus <= 0 || frame_host->n_jobs <= 0) return;
     vvc355_gpm_frame_build(stream, frame_dev, frame_host);
+    vvc355_gpm_frame_predict(stream, bd, frame_dev, frame_host);
+}
+
+void vvc355_gpm_frame_predict(void *stream, int bd, const vvc355_gpm_frame *, const vvc355_gpm_frame *frame_host)
+{
+    if (frame_host->n_cus <= 0 || frame_host->n_jobs <= 0) return;
     vvc355_gpm_batch(stream, bd, (const vvc355_gpm_job *)frame_host->jobs, frame_host->n_jobs);
 }
 
@@ -482,6 +495,15 @@ int vvc355_ciip_frame_pass(void *stream, int bd, const vvc355_ciip_frame *frame_
         return err;
     if (frame_host->n_cus == 0 || frame_host->n_jobs == 0) return 0;
     vvc355_ciip_frame_build(stream, frame_dev, frame_host);
+    return vvc355_ciip_frame_predict(stream, bd, frame_dev, frame_host);
+}
+
+int vvc355_ciip_frame_predict(void *stream, int bd, const vvc355_ciip_frame *frame_dev, const vvc355_ciip_frame *frame_host)
+{
+    const int err = frame_dev ? vvc355::ciip_frame_check(frame_host, bd) : VVC355_CIIP_E_FRAME;
+    if (err)
+        return err;
+    if (frame_host->n_cus == 0 || frame_host->n_jobs == 0) return 0;
     vvc355::ciip_pred_launch((hipStream_t)stream, bd, (const vvc355_bipred_job *)frame_host->jobs, frame_host->n_jobs);
     return 0;
 }

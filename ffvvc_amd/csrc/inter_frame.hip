@@ -100,6 +100,12 @@ void vvc355_inter_frame_pass(void *stream, int bd, const vvc355_inter_frame *fra
 {
     if (frame_host->n_pus <= 0 || frame_host->n_jobs <= 0) return;
     vvc355_inter_frame_build(stream, frame_dev, frame_host);
+    vvc355_inter_frame_predict(stream, bd, frame_dev, frame_host);
+}
+
+void vvc355_inter_frame_predict(void *stream, int bd, const vvc355_inter_frame *frame_dev, const vvc355_inter_frame *frame_host)
+{
+    if (frame_host->n_pus <= 0 || frame_host->n_jobs <= 0) return;
     vvc355_bipred_batch(stream, bd, (const vvc355_bipred_job *)frame_host->jobs_luma, frame_host->n_jobs);
     if (frame_host->dmvr_mvf) {
         hipLaunchKernelGGL(vvc355::inter_dmvr_info_kernel, dim3((frame_host->n_jobs + 255) / 256), dim3(256), 0, (hipStream_t)stream, frame_dev);

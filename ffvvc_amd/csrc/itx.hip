@@ -12,6 +12,7 @@
 #include "runtime.hpp"
 #include "resid_math.hpp"
 #include "../../include/vvc_mi355.h"
+#include "stage_checks.hpp"
 
 namespace vvc355 {
 
@@ -1473,6 +1474,76 @@ static void launch_ts_tb(hipStream_t st, const vvc355_ts_tb_frame *fd, const vvc
 
 } // namespace vvc355
 
+// The host checks of the three TB record passes, as the header states them (also run by vvc355_picture_pass for the whole picture)
+int vvc355::intra_tb_check(const vvc355_intra_tb_frame *frame_host)
+{
+    if (!frame_host || frame_host->n_tus < 0 || frame_host->class_first[0] != 0 || frame_host->class_first[5] != frame_host->n_tus)
+        return VVC355_INTRA_TB_E_CLASS;
+    for (int k = 0; k < 5; k++)
+        if (frame_host->class_first[k] > frame_host->class_first[k + 1])
+            return VVC355_INTRA_TB_E_CLASS;
+    if (frame_host->bd != 8 && frame_host->bd != 10 && frame_host->bd != 12)
+        return VVC355_INTRA_TB_E_BD;
+    if (frame_host->range < 15 || frame_host->range > 20)
+        return VVC355_INTRA_TB_E_RANGE;
+    if (!frame_host->lv != !frame_host->levels)
+        return VVC355_INTRA_TB_E_LEVELS;
+    if (frame_host->launch_mode > 2)
+        return VVC355_INTRA_TB_E_MODE;
+    return 0;
+}
+
+int vvc355::inter_tb_check(const vvc355_inter_tb_frame *f, int channels)
+{
+    if (!f || f->n_tus < 0 || f->bin_first[0][0] != 0 || f->bin_first[0][VVC355_INTER_TB_BINS] != f->bin_first[1][0] ||
+        f->bin_first[1][VVC355_INTER_TB_BINS] != f->n_tus)
+        return VVC355_INTER_TB_E_BINS;
+    for (int ch = 0; ch < 2; ch++)
+        for (int k = 0; k < VVC355_INTER_TB_BINS; k++)
+            if (f->bin_first[ch][k] > f->bin_first[ch][k + 1])
+                return VVC355_INTER_TB_E_BINS;
+    if (f->bd != 8 && f->bd != 10 && f->bd != 12)
+        return VVC355_INTER_TB_E_BD;
+    if (f->range < 15 || f->range > 20)
+        return VVC355_INTER_TB_E_RANGE;
+    if (!f->lv != !f->levels)
+        return VVC355_INTER_TB_E_LEVELS;
+    if (f->scale_table && f->size_y != 32 && f->size_y != 64)
+        return VVC355_INTER_TB_E_SIZE_Y;
+    if (f->hs > 1 || f->vs > 1)
+        return VVC355_INTER_TB_E_SHIFT;
+    if (channels < 1 || channels > 3)
+        return VVC355_INTER_TB_E_CHANNELS;
+    if (channels == 3 && f->scale_table)
+        return VVC355_INTER_TB_E_ORDER;
+    return 0;
+}
+
+int vvc355::ts_tb_check(const vvc355_ts_tb_frame *f, int channels)
+{
+    if (!f || f->n_tus < 0 || f->class_first[0][0] != 0 || f->class_first[0][4] != f->class_first[1][0] || f->class_first[1][4] != f->n_tus)
+        return VVC355_TS_TB_E_CLASS;
+    for (int ch = 0; ch < 2; ch++)
+        for (int k = 0; k < 4; k++)
+            if (f->class_first[ch][k] > f->class_first[ch][k + 1])
+                return VVC355_TS_TB_E_CLASS;
+    if (f->bd != 8 && f->bd != 10 && f->bd != 12)
+        return VVC355_TS_TB_E_BD;
+    if (f->range < 15 || f->range > 20)
+        return VVC355_TS_TB_E_RANGE;
+    if (!f->lv != !f->levels)
+        return VVC355_TS_TB_E_LEVELS;
+    if (f->scale_table && f->size_y != 32 && f->size_y != 64)
+        return VVC355_TS_TB_E_SIZE_Y;
+    if (f->hs > 1 || f->vs > 1)
+        return VVC355_TS_TB_E_SHIFT;
+    if (channels < 1 || channels > 3)
+        return VVC355_TS_TB_E_CHANNELS;
+    if (channels == 3 && f->scale_table)
+        return VVC355_TS_TB_E_ORDER;
+    return 0;
+}
+
 using namespace vvc355;
 
 extern "C" {
@@ -1502,19 +1573,9 @@ void vvc355_itx_frame_build(void *stream, const vvc355_itx_frame *frame_dev, con
 int vvc355_intra_tb_pass(void *stream, const vvc355_intra_tb_frame *frame_dev, const vvc355_intra_tb_frame *frame_host)
 {
     // the host copy is checked before any HIP call: a refused frame launches nothing
-    if (!frame_host || frame_host->n_tus < 0 || frame_host->class_first[0] != 0 || frame_host->class_first[5] != frame_host->n_tus)
-        return VVC355_INTRA_TB_E_CLASS;
-    for (int k = 0; k < 5; k++)
-        if (frame_host->class_first[k] > frame_host->class_first[k + 1])
-            return VVC355_INTRA_TB_E_CLASS;
-    if (frame_host->bd != 8 && frame_host->bd != 10 && frame_host->bd != 12)
-        return VVC355_INTRA_TB_E_BD;
-    if (frame_host->range < 15 || frame_host->range > 20)
-        return VVC355_INTRA_TB_E_RANGE;
-    if (!frame_host->lv != !frame_host->levels)
-        return VVC355_INTRA_TB_E_LEVELS;
-    if (frame_host->launch_mode > 2)
-        return VVC355_INTRA_TB_E_MODE;
+    const int err = intra_tb_check(frame_host);
+    if (err)
+        return err;
     if (frame_host->n_tus == 0)
         return 0;
     const int mode = frame_host->launch_mode ? frame_host->launch_mode : kIntraTbDefaultMode;
@@ -1530,27 +1591,9 @@ int vvc355_inter_tb_pass(void *stream, const vvc355_inter_tb_frame *frame_dev, c
 {
     // the host copy is checked before any HIP call: a refused frame launches nothing
     const vvc355_inter_tb_frame *f = frame_host;
-    if (!f || f->n_tus < 0 || f->bin_first[0][0] != 0 || f->bin_first[0][VVC355_INTER_TB_BINS] != f->bin_first[1][0] ||
-        f->bin_first[1][VVC355_INTER_TB_BINS] != f->n_tus)
-        return VVC355_INTER_TB_E_BINS;
-    for (int ch = 0; ch < 2; ch++)
-        for (int k = 0; k < VVC355_INTER_TB_BINS; k++)
-            if (f->bin_first[ch][k] > f->bin_first[ch][k + 1])
-                return VVC355_INTER_TB_E_BINS;
-    if (f->bd != 8 && f->bd != 10 && f->bd != 12)
-        return VVC355_INTER_TB_E_BD;
-    if (f->range < 15 || f->range > 20)
-        return VVC355_INTER_TB_E_RANGE;
-    if (!f->lv != !f->levels)
-        return VVC355_INTER_TB_E_LEVELS;
-    if (f->scale_table && f->size_y != 32 && f->size_y != 64)
-        return VVC355_INTER_TB_E_SIZE_Y;
-    if (f->hs > 1 || f->vs > 1)
-        return VVC355_INTER_TB_E_SHIFT;
-    if (channels < 1 || channels > 3)
-        return VVC355_INTER_TB_E_CHANNELS;
-    if (channels == 3 && f->scale_table)
-        return VVC355_INTER_TB_E_ORDER;
+    const int err = inter_tb_check(f, channels);
+    if (err)
+        return err;
     if (f->n_tus == 0)
         return 0;
     VVC355_BD_DISPATCH(f->bd, launch_inter_tb<BD>((hipStream_t)stream, frame_dev, *f, channels));
@@ -1562,26 +1605,9 @@ int vvc355_ts_tb_pass(void *stream, const vvc355_ts_tb_frame *frame_dev, const v
 {
     // the host copy is checked before any HIP call: a refused frame launches nothing
     const vvc355_ts_tb_frame *f = frame_host;
-    if (!f || f->n_tus < 0 || f->class_first[0][0] != 0 || f->class_first[0][4] != f->class_first[1][0] || f->class_first[1][4] != f->n_tus)
-        return VVC355_TS_TB_E_CLASS;
-    for (int ch = 0; ch < 2; ch++)
-        for (int k = 0; k < 4; k++)
-            if (f->class_first[ch][k] > f->class_first[ch][k + 1])
-                return VVC355_TS_TB_E_CLASS;
-    if (f->bd != 8 && f->bd != 10 && f->bd != 12)
-        return VVC355_TS_TB_E_BD;
-    if (f->range < 15 || f->range > 20)
-        return VVC355_TS_TB_E_RANGE;
-    if (!f->lv != !f->levels)
-        return VVC355_TS_TB_E_LEVELS;
-    if (f->scale_table && f->size_y != 32 && f->size_y != 64)
-        return VVC355_TS_TB_E_SIZE_Y;
-    if (f->hs > 1 || f->vs > 1)
-        return VVC355_TS_TB_E_SHIFT;
-    if (channels < 1 || channels > 3)
-        return VVC355_TS_TB_E_CHANNELS;
-    if (channels == 3 && f->scale_table)
-        return VVC355_TS_TB_E_ORDER;
+    const int err = ts_tb_check(f, channels);
+    if (err)
+        return err;
     if (f->n_tus == 0)
         return 0;
     VVC355_BD_DISPATCH(f->bd, launch_ts_tb<BD>((hipStream_t)stream, frame_dev, *f, channels));

@@ -8,6 +8,7 @@
 #include "runtime.hpp"
 #include "bs_rules.hpp"
 #include "../../include/vvc_mi355.h"
+#include "stage_checks.hpp"
 
 namespace vvc355 {
 
@@ -51,6 +52,58 @@ __global__ __launch_bounds__(256) void lmcs_kernel(const vvc355_blend_job *__res
         const int y = i / wt, x = x_tail + i - y * wt;
         uint8_t *row = dst + row_off(y, job.dst_stride);
         st_px<BD>(row, x, lut_lds[ld_px<BD>(row, x)]);
+    }
+}
+
+// ff_vvc_lmcs_filter (vvc_filter.c:1322) for every CTB of a picture: workgroup (blockIdx.x = CTB in raster order, blockIdx.y = its slab
+// of the CTB's samples) looks up its CTB's slice and leaves before staging anything when the slice does not use LMCS or the CTB is a hole
+// (slice_idx outside [0, n_slices)).  Otherwise as lmcs_kernel: the LUT in LDS once per workgroup, 8-sample vectors where the rows are
+// vector-aligned (a CTB's first column always is: 32 samples or more from the plane's), per-sample accesses for the rest.  The
+// rectangle is the CTB clipped to the picture, so nothing outside [0, width) x [0, height) is touched.
+template <int BD>
+__global__ __launch_bounds__(256) void lmcs_frame_kernel(const vvc355_lmcs_frame *__restrict__ fp)
+{
+    using px_t = typename Px<BD>::type;
+    constexpr int VB = 8 * (int)sizeof(px_t);                 // bytes per 8-sample vector
+    __shared__ __attribute__((aligned(16))) px_t lut_lds[1 << BD];
+    const vvc355_lmcs_frame f = load_uniform(fp);
+    const int rs = blockIdx.x;                                // < ctb_width * ctb_height: the grid is exactly that wide
+    const int slice = gld<int16_t>((const int16_t *)f.slice_idx + rs);
+    if (slice < 0 || slice >= f.n_slices)
+        return;
+    if (!gld<uint8_t>((const uint8_t *)f.slice_lmcs_used + slice))
+        return;
+    const uint8_t *lut = (const uint8_t *)f.inv_lut;
+    if ((f.inv_lut & 15) == 0) {
+        for (int i = threadIdx.x; i < (int)((sizeof(px_t) << BD) / 16); i += 256)
+            ((uint4 *)lut_lds)[i] = gld<uint4>(lut + i * 16);
+    } else {
+        for (int i = threadIdx.x; i < (1 << BD); i += 256)
+            lut_lds[i] = (px_t)ld_px<BD>(lut, i);
+    }
+    __syncthreads();
+    const int ry = rs / f.ctb_width, rx = rs - ry * f.ctb_width;
+    const int x0 = rx << f.ctb_log2, y0 = ry << f.ctb_log2;
+    const int w = min(1 << f.ctb_log2, f.width - x0), h = min(1 << f.ctb_log2, f.height - y0);
+    uint8_t *dst = (uint8_t *)f.plane + row_off(y0, f.stride) + x0 * (int)sizeof(px_t);
+    const bool vec = ((f.plane | (uint64_t)(uint32_t)f.stride) & (VB - 1)) == 0;
+    const int wv = vec ? w >> 3 : 0;                          // whole vectors per row
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < wv * h; i += gridDim.y * 256) {
+        const int y = i / wv, xv = i - y * wv;
+        uint8_t *p = dst + row_off(y, f.stride) + xv * VB;
+        px_t t[8];
+        if (BD > 8) { const uint4 q = gld<uint4>(p); __builtin_memcpy(t, &q, sizeof(t)); }
+        else { const uint2 q = gld<uint2>(p); __builtin_memcpy(t, &q, sizeof(t)); }
+#pragma unroll
+        for (int k = 0; k < 8; k++) t[k] = lut_lds[t[k] & ((1 << BD) - 1)];
+        if (BD > 8) { uint4 q; __builtin_memcpy(&q, t, sizeof(t)); gst<uint4>(p, q); }
+        else { uint2 q; __builtin_memcpy(&q, t, sizeof(t)); gst<uint2>(p, q); }
+    }
+    const int x_tail = wv * 8, wt = w - x_tail;               // columns left to the per-sample path
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < wt * h; i += gridDim.y * 256) {
+        const int y = i / wt, x = x_tail + i - y * wt;
+        uint8_t *row = dst + row_off(y, f.stride);
+        st_px<BD>(row, x, lut_lds[ld_px<BD>(row, x) & ((1 << BD) - 1)]);
     }
 }
 
@@ -1057,6 +1110,31 @@ __global__ __launch_bounds__(256) void deblock_bs_kernel(const vvc355_bs_frame *
 
 } // namespace vvc355
 
+// the inverse-LMCS frame as the header states it: every refusal before any HIP call
+int vvc355::lmcs_frame_check(const vvc355_lmcs_frame *f, int bd)
+{
+    if (!f)
+        return VVC355_LMCS_FRAME_E_FRAME;
+    if (bd != 8 && bd != 10 && bd != 12)
+        return VVC355_LMCS_FRAME_E_BD;
+    if (f->width <= 0 || f->height <= 0 || f->width >= (1 << 16) || f->height >= (1 << 16))
+        return VVC355_LMCS_FRAME_E_SIZE;
+    if (f->ctb_log2 < 5 || f->ctb_log2 > 7)
+        return VVC355_LMCS_FRAME_E_CTB;
+    const int ctb = 1 << f->ctb_log2;
+    if (f->ctb_width != (f->width + ctb - 1) >> f->ctb_log2 || f->ctb_height != (f->height + ctb - 1) >> f->ctb_log2)
+        return VVC355_LMCS_FRAME_E_GRID;
+    const int px = bd > 8 ? 2 : 1;
+    // row_off() is exact for strides below 2^23 and planes below 2 GiB
+    if (f->stride < f->width * px || f->stride % px || f->stride >= (1 << 23) || (int64_t)f->stride * f->height >= ((int64_t)1 << 31))
+        return VVC355_LMCS_FRAME_E_STRIDE;
+    if (f->n_slices < 0)
+        return VVC355_LMCS_FRAME_E_COUNT;
+    if (!f->plane || !f->inv_lut || !f->slice_idx || !f->slice_lmcs_used)
+        return VVC355_LMCS_FRAME_E_TABLES;
+    return 0;
+}
+
 using namespace vvc355;
 
 extern "C" {
@@ -1144,6 +1222,19 @@ void vvc355_lmcs_batch(void *stream, int bd, const vvc355_blend_job *jobs_dev, i
     const int gx = max(1, min(64, (max_w * max_h + 8191) / 8192));      // 4 vectors of 8 samples per lane
     VVC355_BD_DISPATCH(bd, hipLaunchKernelGGL((lmcs_kernel<BD>), dim3(gx, n_jobs), dim3(256), 0, (hipStream_t)stream, jobs_dev));
     HIP_CHECK(hipGetLastError());
+}
+
+int vvc355_lmcs_frame_pass(void *stream, int bd, const vvc355_lmcs_frame *frame_dev, const vvc355_lmcs_frame *frame_host)
+{
+    const int err = frame_dev ? lmcs_frame_check(frame_host, bd) : VVC355_LMCS_FRAME_E_FRAME;
+    if (err)
+        return err;
+    const int ctb = 1 << frame_host->ctb_log2;
+    const int gy = max(1, ctb * ctb / 8192);                             // as vvc355_lmcs_batch: 4 vectors of 8 samples per lane
+    VVC355_BD_DISPATCH(bd, hipLaunchKernelGGL((lmcs_frame_kernel<BD>), dim3(frame_host->ctb_width * frame_host->ctb_height, gy), dim3(256), 0,
+                                              (hipStream_t)stream, frame_dev));
+    HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 void vvc355_lmcs_filter(int bd, uint8_t *dst, ptrdiff_t dst_stride, int width, int height, const uint8_t *lut)

@@ -18,6 +18,7 @@
 #include "runtime.hpp"
 #include "rec_map.hpp"
 #include "../../include/vvc_mi355.h"
+#include "stage_checks.hpp"
 
 namespace vvc355 {
 
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(256) void qp_rec_kernel(const vvc355_qp_rec_frame *
 } // namespace vvc355
 
 // the frame as the header states it: every refusal before any HIP call
-static int qp_rec_check(const vvc355_qp_rec_frame *f)
+int vvc355::qp_rec_check(const vvc355_qp_rec_frame *f)
 {
     if (!f)
         return VVC355_QP_REC_E_FRAME;
@@ -125,7 +126,7 @@ static int qp_rec_check(const vvc355_qp_rec_frame *f)
 
 extern "C" int vvc355_deblock_qp_rec_pass(void *stream, const vvc355_qp_rec_frame *frame_dev, const vvc355_qp_rec_frame *frame_host)
 {
-    const int err = frame_dev ? qp_rec_check(frame_host) : VVC355_QP_REC_E_FRAME;
+    const int err = frame_dev ? vvc355::qp_rec_check(frame_host) : VVC355_QP_REC_E_FRAME;
     if (err)
         return err;
     hipLaunchKernelGGL(vvc355::qp_rec_kernel, dim3(frame_host->ctb_width * frame_host->ctb_height), dim3(256), 0, (hipStream_t)stream, frame_dev);

@@ -1,5 +1,6 @@
 // Runtime helper entries of the C ABI (device memory, streams) — see include/vvc_mi355.h.
 #include <algorithm>
+#include <cstdint>
 #include <queue>
 #include <utility>
 #include <vector>
@@ -59,6 +60,23 @@ void *vvc355_graph_end(void *stream)
 }
 void vvc355_graph_launch(void *graph_exec, void *stream) { HIP_CHECK(hipGraphLaunch((hipGraphExec_t)graph_exec, (hipStream_t)stream)); }
 void vvc355_graph_destroy(void *graph_exec) { HIP_CHECK(hipGraphExecDestroy((hipGraphExec_t)graph_exec)); }
+void *vvc355_event_create(void)
+{
+    hipEvent_t e = nullptr;
+    HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return (void *)e;
+}
+void vvc355_event_destroy(void *event) { HIP_CHECK(hipEventDestroy((hipEvent_t)event)); }
+void vvc355_event_record(void *event, void *stream) { HIP_CHECK(hipEventRecord((hipEvent_t)event, (hipStream_t)stream)); }
+void vvc355_stream_wait_event(void *stream, void *event) { HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)event, 0)); }
+int vvc355_event_query(void *event)
+{
+    const hipError_t e = hipEventQuery((hipEvent_t)event);
+    if (e == hipErrorNotReady)
+        return 0;
+    HIP_CHECK(e);
+    return e == hipSuccess;
+}
 // ---- vvc355_recon_order: critical-path-first ticket order of the in-order pass (host only; see include/vvc_mi355.h)
 namespace {
 // the CTUs `rs` waits for, as recon_one_ctu / recon_light_ctu (intra.hip) do: neighbours that have commands
@@ -121,6 +139,38 @@ int vvc355_recon_order(const vvc355_recon_ctu *ctus, int ncx, int ncy, int32_t *
         }
     }
     return n_work;
+}
+
+// is `order` one the in-order pass can run?  (host only, O(n): every CTU has at most four predecessors)
+int vvc355_recon_order_check(const vvc355_recon_ctu *ctus, int ncx, int ncy, const int32_t *order, int n_work)
+{
+    if (!ctus || ncx < 0 || ncy < 0 || n_work < 0 || (n_work > 0 && !order) || (int64_t)ncx * ncy > INT32_MAX)
+        return VVC355_RECON_ORDER_E_ARGS;
+    const int n = ncx * ncy;
+    std::vector<int32_t> pos(n, -1);        // a CTU's place in the order
+    for (int i = 0; i < n_work; i++) {
+        const int32_t rs = order[i];
+        if (rs < 0 || rs >= n)
+            return VVC355_RECON_ORDER_E_RANGE;
+        if (!ctus[rs].n_cmd)
+            return VVC355_RECON_ORDER_E_EMPTY;
+        if (pos[rs] >= 0)
+            return VVC355_RECON_ORDER_E_DUPLICATE;
+        pos[rs] = i;
+    }
+    for (int rs = 0; rs < n; rs++)
+        if (ctus[rs].n_cmd && pos[rs] < 0)
+            return VVC355_RECON_ORDER_E_MISSING;
+    int dep[4];
+    for (int rs = 0; rs < n; rs++) {
+        if (!ctus[rs].n_cmd)
+            continue;
+        const int nd = recon_deps(ctus, ncx, rs, dep);
+        for (int i = 0; i < nd; i++)
+            if (pos[dep[i]] > pos[rs])
+                return VVC355_RECON_ORDER_E_DEPENDENCY;
+    }
+    return 0;
 }
 
 const char *vvc355_version(void) { return "vvc_mi355 0.1 (gfx950)"; }

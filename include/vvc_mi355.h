@@ -55,6 +55,14 @@ void  vvc355_graph_begin(void *stream);
 void *vvc355_graph_end(void *stream);
 void  vvc355_graph_launch(void *graph_exec, void *stream);
 void  vvc355_graph_destroy(void *graph_exec);
+/* Events: how one picture waits for another across streams — what the reference does with ff_vvc_report_progress / ff_vvc_add_progress_listener
+ * (libavcodec/vvc/vvc_refs.c:532, :552; vvc_thread.c:252) on the host.  Created with timing disabled.  vvc355_event_query: 1 = everything recorded before the
+ * event has finished, 0 = not yet.  All under the error policy above. */
+void *vvc355_event_create(void);
+void  vvc355_event_destroy(void *event);
+void  vvc355_event_record(void *event, void *stream);
+void  vvc355_stream_wait_event(void *stream, void *event);
+int   vvc355_event_query(void *event);
 const char *vvc355_version(void);
 
 /* ------------------------------------------------------------------ constant tables (tables.cpp) */
@@ -237,6 +245,29 @@ void vvc355_sao_ctb_batch(void *stream, int bd, const vvc355_sao_job *jobs_dev, 
 void vvc355_deblock_batch(void *stream, int bd, const vvc355_deblock_job *jobs_dev, int n_jobs);
 /* blend_job: dst = luma rectangle (in place), src0 = LUT of 2^bd pixel-typed entries */
 void vvc355_lmcs_batch(void *stream, int bd, const vvc355_blend_job *jobs_dev, int n_jobs, int max_w, int max_h);
+
+/*
+ * Inverse luma mapping of a whole picture: ff_vvc_lmcs_filter (vvc_filter.c:1322) for every CTB in one launch — lmcs.filter over the CTB's
+ * part of the picture with fc->ps.lmcs.inv_lut where the CTB's slice has sh_lmcs_used_flag.  No job array: a workgroup finds its CTB's slice
+ * itself.  A CTB whose slice_idx is outside [0, n_slices) is a hole and is left alone, like a CTB of a slice that does not use LMCS.
+ * Nothing outside [0, width) x [0, height) is read or written; the pitch padding keeps its bytes.  No implicit padding: 64 bytes.
+ */
+typedef struct vvc355_lmcs_frame {
+    uint64_t plane;          /* DEVICE luma plane, mapped in place */
+    uint64_t inv_lut;        /* DEVICE fc->ps.lmcs.inv_lut, 1 << bd pixel-typed entries */
+    uint64_t slice_idx;      /* DEVICE int16 per CTB, as in the other frames */
+    uint64_t slice_lmcs_used;/* DEVICE uint8 per slice: sh_lmcs_used_flag */
+    int32_t  stride, width, height, ctb_width, ctb_height, n_slices;
+    uint8_t  ctb_log2, pad_[3];
+} vvc355_lmcs_frame;
+/* what vvc355_lmcs_frame_pass returns for a frame it refuses: no frame; bd not 8 / 10 / 12; width or height <= 0 or beyond 65535; ctb_log2 outside
+ * 5..7; ctb_width / ctb_height not ceil(size >> ctb_log2); a stride smaller than a row, no multiple of the pixel size, 8 MiB or more, or a
+ * plane of 2 GiB or more; n_slices < 0; plane, inv_lut, slice_idx or slice_lmcs_used missing */
+enum { VVC355_LMCS_FRAME_E_FRAME = -1, VVC355_LMCS_FRAME_E_BD = -2, VVC355_LMCS_FRAME_E_SIZE = -3, VVC355_LMCS_FRAME_E_CTB = -4,
+       VVC355_LMCS_FRAME_E_GRID = -5, VVC355_LMCS_FRAME_E_STRIDE = -6, VVC355_LMCS_FRAME_E_COUNT = -7, VVC355_LMCS_FRAME_E_TABLES = -8 };
+/* One launch on `stream`.  The host copy of the frame is checked before any HIP call.
+ * returns 0, or a negative VVC355_LMCS_FRAME_E_* with NOTHING launched */
+int vvc355_lmcs_frame_pass(void *stream, int bd, const vvc355_lmcs_frame *frame_dev, const vvc355_lmcs_frame *frame_host);
 
 /* VVCLMCSDSPContext.filter — vvcdsp.h:124, vvc_filter_template.c:25 */
 void vvc355_lmcs_filter(int bd, uint8_t *dst, ptrdiff_t dst_stride, int width, int height, const uint8_t *lut);
@@ -869,7 +900,10 @@ typedef struct vvc355_inter_frame {
 } vvc355_inter_frame;
 /* job arrays only (then vvc355_bipred_batch on jobs_luma, vvc355_bipred_chroma_batch on jobs_chroma) */
 void vvc355_inter_frame_build(void *stream, const vvc355_inter_frame *frame_dev, const vvc355_inter_frame *frame_host);
-/* build + luma + chroma */
+/* what _pass launches after its build: luma (DMVR + BDOF), set_dmvr_info (vvc_inter.c:750-762) when dmvr_mvf is set, chroma — the half that
+ * reads the reference pictures (the build reads only the uploaded tables) */
+void vvc355_inter_frame_predict(void *stream, int bd, const vvc355_inter_frame *frame_dev, const vvc355_inter_frame *frame_host);
+/* build + predict */
 void vvc355_inter_frame_pass(void *stream, int bd, const vvc355_inter_frame *frame_dev, const vvc355_inter_frame *frame_host);
 
 /* ------------------------------------------------------------------ affine and geometric-partition stage drivers (inter_cu.hip) */
@@ -909,7 +943,9 @@ typedef struct vvc355_affine_frame {
 } vvc355_affine_frame;
 /* job arrays only */
 void vvc355_affine_frame_build(void *stream, const vvc355_affine_frame *frame_dev, const vvc355_affine_frame *frame_host);
-/* build, then vvc355_affine_batch on jobs_luma and vvc355_bipred_chroma_batch on jobs_chroma */
+/* vvc355_affine_batch on jobs_luma and vvc355_bipred_chroma_batch on jobs_chroma: pred_affine_blk (vvc_inter.c:828-873) once the jobs exist */
+void vvc355_affine_frame_predict(void *stream, int bd, const vvc355_affine_frame *frame_dev, const vvc355_affine_frame *frame_host);
+/* build, then predict */
 void vvc355_affine_frame_pass(void *stream, int bd, const vvc355_affine_frame *frame_dev, const vvc355_affine_frame *frame_host);
 
 typedef struct vvc355_gpm_cu {
@@ -928,7 +964,9 @@ typedef struct vvc355_gpm_frame {
 } vvc355_gpm_frame;
 /* job arrays only */
 void vvc355_gpm_frame_build(void *stream, const vvc355_gpm_frame *frame_dev, const vvc355_gpm_frame *frame_host);
-/* build, then vvc355_gpm_batch */
+/* vvc355_gpm_batch on jobs: pred_gpm_blk (vvc_inter.c:466-527) once the jobs exist */
+void vvc355_gpm_frame_predict(void *stream, int bd, const vvc355_gpm_frame *frame_dev, const vvc355_gpm_frame *frame_host);
+/* build, then predict */
 void vvc355_gpm_frame_pass(void *stream, int bd, const vvc355_gpm_frame *frame_dev, const vvc355_gpm_frame *frame_host);
 /* HOST only (no HIP call): the (cb_width >> hs) x (cb_height >> vs) weights, 0 .. 8, row-major into out, that the jobs the GPM
  * builder writes read for a component of a coding unit of this partition and size: the same masks and the same addressing */
@@ -1004,7 +1042,10 @@ enum { VVC355_CIIP_E_FRAME = -1, VVC355_CIIP_E_SIZE = -2, VVC355_CIIP_E_CTB = -3
  * captured with vvc355_graph_begin / _end. */
 /* job array + command patch only */
 int vvc355_ciip_frame_build(void *stream, const vvc355_ciip_frame *frame_dev, const vvc355_ciip_frame *frame_host);
-/* build, then ONE prediction launch over jobs[0 .. n_jobs), luma and chroma tiles together */
+/* ONE prediction launch over jobs[0 .. n_jobs), luma and chroma tiles together (the inter operand of ff_vvc_predict_ciip, vvc_inter.c:915);
+ * the frame is checked as _pass checks it */
+int vvc355_ciip_frame_predict(void *stream, int bd, const vvc355_ciip_frame *frame_dev, const vvc355_ciip_frame *frame_host);
+/* build, then predict */
 int vvc355_ciip_frame_pass(void *stream, int bd, const vvc355_ciip_frame *frame_dev, const vvc355_ciip_frame *frame_host);
 
 /* ------------------------------------------------------------------ affine sub-blocks with PROF (affine.hip) */
@@ -1423,6 +1464,71 @@ size_t vvc355_recon_state_bytes(int n_ctus);
  */
 int vvc355_recon_order(const vvc355_recon_ctu *ctus_host, int ctb_width, int ctb_height, int32_t *order_host);
 void vvc355_recon_frame_pass(void *stream, int bd, const vvc355_recon_frame *frame_dev, const vvc355_recon_frame *frame_host);
+/*
+ * HOST helper, O(n), no device work: is order_host[0 .. n_work) a ticket order vvc355_recon_frame_pass can run?  The pass takes the order on
+ * trust, and a CTU placed before a CTU it waits for makes its workgroup spin on a flag nobody is left to set: a GPU hang, not an error (the
+ * reference's scheduler cannot get there: it derives the order itself, vvc_thread.c:156-184).  Returns 0 when the order lists every CTU
+ * that has commands exactly once, no other CTU, and every CTU after the CTUs it waits for (the rule of the flags above, the one
+ * vvc355_recon_order uses); otherwise what is wrong first: arguments (no table, no order with n_work > 0, a grid or n_work below 0); an
+ * index outside the grid; a CTU without commands; a CTU listed twice; a CTU with commands not listed; a CTU ahead of one it waits for.
+ */
+enum { VVC355_RECON_ORDER_E_ARGS = -1, VVC355_RECON_ORDER_E_RANGE = -2, VVC355_RECON_ORDER_E_EMPTY = -3, VVC355_RECON_ORDER_E_DUPLICATE = -4,
+       VVC355_RECON_ORDER_E_MISSING = -5, VVC355_RECON_ORDER_E_DEPENDENCY = -6 };
+int vvc355_recon_order_check(const vvc355_recon_ctu *ctus_host, int ctb_width, int ctb_height, const int32_t *order_host, int n_work);
+
+/* ------------------------------------------------------------------ one picture, one call (picture.cpp) */
+
+/*
+ * The launch sequence of a picture's record-path stages: what the reference spreads over its per-CTU task stages (vvc_thread.c:432-565, :592-598:
+ * run_inter, run_recon, run_lmcs, run_deblock_v, run_deblock_h, run_sao, run_alf) and their progress waits, as one host call on one stream.  Every stage is a pair
+ * (DEVICE address, HOST address) of the frame descriptor its own entry takes; host == 0 skips the stage.  Order:
+ *   before the reference waits (these read only uploaded records):
+ *     tab_fill, the inter / affine / gpm / ciip BUILDS, intra_tb, bs_rec, qp_rec, the ALF build
+ *   the stream waits for refs[0 .. n_refs)
+ *   after them:
+ *     the inter / affine / gpm / ciip PREDICTS,
+ *     inter_tb and ts_tb: with channels 3 each; with a lmcs_scale stage inter_tb(1), ts_tb(1), lmcs_vpdu_scale_pass, inter_tb(2), ts_tb(2),
+ *     recon, lmcs (inverse mapping), deblock_v, deblock_h, sao, the ALF filter, and `done` is recorded.
+ * The WHOLE picture is validated before the first launch: every stage's own host check (the stages that return a code), a stage given
+ * without a device address, vvc355_recon_order_check on recon_ctus_host / recon_order_host where both are given (with the recon frame's
+ * grid and n_work), and the picture's own rules — ciip.cmds, when set, is recon.cmds; a scale_table of inter_tb / ts_tb is lmcs_scale.scale
+ * and that stage is present; n_refs is 0..32 and no reference is 0; while `stream` is capturing a graph n_refs and done are 0 (a captured
+ * wait would tie the graph to one event).  On a refusal NOTHING is launched and no event is touched; the value is
+ * -(stage << 8 | -code): VVC355_PIC_STAGE(r) gives the VVC355_PIC_STAGE_* id and VVC355_PIC_CODE(r) the stage's own negative code (every
+ * code of every stage fits 8 bits).  A picture with no stage, no reference and no `done` returns 0 without any HIP call.
+ * `pic` and the descriptors it names are HOST memory and are read during the call only.  No implicit padding: 568 bytes.
+ */
+typedef struct vvc355_stage_ref { uint64_t dev, host; } vvc355_stage_ref;
+typedef struct vvc355_picture {
+    vvc355_stage_ref tab_fill;     /* vvc355_tab_fill (the motion records; any of its tables) */
+    vvc355_stage_ref inter, affine, gpm, ciip;     /* vvc355_inter_frame, _affine_frame, _gpm_frame, _ciip_frame */
+    vvc355_stage_ref intra_tb;     /* vvc355_intra_tb_frame */
+    vvc355_stage_ref bs_rec, qp_rec;               /* vvc355_bs_rec_frame, vvc355_qp_rec_frame */
+    vvc355_stage_ref alf;          /* vvc355_alf_frame; needs alf_work */
+    vvc355_stage_ref inter_tb, ts_tb;              /* vvc355_inter_tb_frame, vvc355_ts_tb_frame */
+    vvc355_stage_ref lmcs_scale;   /* vvc355_lmcs_scale_frame: chroma residual scaling, splits the TB passes into luma / chroma calls */
+    vvc355_stage_ref recon;        /* vvc355_recon_frame */
+    vvc355_stage_ref lmcs;         /* vvc355_lmcs_frame */
+    vvc355_stage_ref deblock_v, deblock_h;         /* vvc355_deblock_frame with vertical = 1 / 0 */
+    vvc355_stage_ref sao;          /* vvc355_sao_frame */
+    uint64_t alf_work;             /* DEVICE scratch of vvc355_alf_frame_work_bytes() */
+    uint64_t recon_ctus_host, recon_order_host;    /* HOST copies of recon.ctus / recon.order, or 0: not checked */
+    uint64_t refs[32];             /* events (vvc355_event_create) of the reference pictures: their `done` */
+    uint64_t done;                 /* event recorded after the last stage ("decoded"), or 0 */
+    int32_t  n_refs, pad_;
+} vvc355_picture;
+enum { VVC355_PIC_STAGE_PICTURE = 1, VVC355_PIC_STAGE_TAB_FILL, VVC355_PIC_STAGE_INTER, VVC355_PIC_STAGE_AFFINE, VVC355_PIC_STAGE_GPM,
+       VVC355_PIC_STAGE_CIIP, VVC355_PIC_STAGE_INTRA_TB, VVC355_PIC_STAGE_BS_REC, VVC355_PIC_STAGE_QP_REC, VVC355_PIC_STAGE_ALF,
+       VVC355_PIC_STAGE_INTER_TB, VVC355_PIC_STAGE_TS_TB, VVC355_PIC_STAGE_LMCS_SCALE, VVC355_PIC_STAGE_RECON, VVC355_PIC_STAGE_RECON_ORDER,
+       VVC355_PIC_STAGE_LMCS, VVC355_PIC_STAGE_DEBLOCK_V, VVC355_PIC_STAGE_DEBLOCK_H, VVC355_PIC_STAGE_SAO };
+/* codes of VVC355_PIC_STAGE_PICTURE (the picture's own rules, checked first); VVC355_PIC_E_NO_DEVICE_FRAME is reported under the id of
+ * the stage that has a host descriptor and no device address (the ALF stage: or no alf_work), before any stage's own check runs */
+enum { VVC355_PIC_E_NO_DEVICE_FRAME = -1, VVC355_PIC_E_PICTURE = -2, VVC355_PIC_E_CIIP_CMDS = -3, VVC355_PIC_E_SCALE_TABLE = -4,
+       VVC355_PIC_E_REFS = -5, VVC355_PIC_E_CAPTURE = -6 };
+#define VVC355_PIC_ERROR(stage, code) (-(((stage) << 8) | -(code)))
+#define VVC355_PIC_STAGE(ret)         ((-(ret)) >> 8)
+#define VVC355_PIC_CODE(ret)          (-((-(ret)) & 255))
+int vvc355_picture_pass(void *stream, int bd, const vvc355_picture *pic);   /* pic is HOST memory */
 
 #ifdef __cplusplus
 }
