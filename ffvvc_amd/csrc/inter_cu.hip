@@ -35,6 +35,9 @@ static_assert(sizeof(vvc355_recon_cmd) == 40 && offsetof(vvc355_recon_cmd, joint
 
 // mc_fused.hip: ciip_pred_kernel<bd> over jobs[0 .. n_jobs), one wave per job
 void ciip_pred_launch(hipStream_t stream, int bd, const vvc355_bipred_job *jobs_dev, int n_jobs);
+// mc_fused.hip: bipred_chroma_one_pair_kernel<bd>, one wave per pair of chroma jobs: what vvc355_bipred_chroma_batch does for arrays
+// that cannot take its four-pairs-per-wave path, without that path's LDS and registers
+void chroma_pairs_launch(hipStream_t stream, int bd, const vvc355_bipred_job *jobs_dev, int n_jobs);
 
 // partition -> angleIdx / distanceIdx and disLut (tables_small.inc; tables.cpp exports the same text as vvc355_tab_gpm_*)
 #define VVC355_TABLE(type, name, count) static constexpr type c_##name[count]
@@ -453,8 +456,8 @@ void vvc355_affine_frame_predict(void *stream, int bd, const vvc355_affine_frame
     if (frame_host->n_cus <= 0 || frame_host->n_jobs <= 0) return;
     vvc355_affine_batch(stream, bd, (const vvc355_affine_job *)frame_host->jobs_luma, frame_host->n_jobs);
     if (frame_host->pic.chroma_format_idc)
-        vvc355_bipred_chroma_batch(stream, bd, (const vvc355_bipred_job *)frame_host->jobs_chroma,
-                                   2 * (frame_host->n_jobs >> (frame_host->pic.hs + frame_host->pic.vs)));
+        vvc355::chroma_pairs_launch((hipStream_t)stream, bd, (const vvc355_bipred_job *)frame_host->jobs_chroma,      // 4x4 blocks: never the quad path
+                                    2 * (frame_host->n_jobs >> (frame_host->pic.hs + frame_host->pic.vs)));
 }
 
 void vvc355_gpm_frame_build(void *stream, const vvc355_gpm_frame *frame_dev, const vvc355_gpm_frame *frame_host)

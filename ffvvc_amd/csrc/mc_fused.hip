@@ -553,22 +553,18 @@ __global__ __launch_bounds__(256) void gpm_kernel(const vvc355_gpm_job *__restri
     bipred_plain<BD>(&base, lds_all[wave], lane, &job);
 }
 
-// Chroma launch: one wave per PAIR of consecutive jobs.  When the two are the Cb and Cr blocks of one sub-block (same
+#include "mc_chroma_quad.hpp"
+
+// One PAIR of consecutive jobs, ia and ia + 1, by one wave.  When the two are the Cb and Cr blocks of one sub-block (same
 // geometry and motion, width <= 8) they are predicted together as one 16-wide block whose halves come from two planes —
 // an 8x8 block alone leaves half of the lanes of the vertical pass and of the window fetch idle.  Any other pair is done one
-// job after the other; jobs that are not chroma are skipped.
+// job after the other; jobs that are not chroma are skipped.  ia is wave-uniform.
 template <int BD>
-__global__ __launch_bounds__(256) void bipred_chroma_pair_kernel(const vvc355_bipred_job *__restrict__ jobs, int n_jobs)
+__device__ __forceinline__ void chroma_pair(const vvc355_bipred_job *__restrict__ jobs, int ia, int n_jobs, BipredLds &L, int lane)
 {
-    __shared__ __attribute__((aligned(16))) BipredLds lds_all[4];
     using px_t = typename Px<BD>::type;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int ia = 2 * (xcd_chunked(blockIdx.x, gridDim.x) * 4 + wave);
-    if (ia >= n_jobs)
-        return;
     const bool has_b = ia + 1 < n_jobs;
     const vvc355_bipred_job ja = load_uniform(jobs + ia), jb = load_uniform(jobs + (has_b ? ia + 1 : ia));
-    BipredLds &L = lds_all[wave];
     const bool bi_a = !(ja.pred_flag == 1 || ja.pred_flag == 2), bi_b = !(jb.pred_flag == 1 || jb.pred_flag == 2);
     bool pair = has_b && bi_a && bi_b && ja.chroma && jb.chroma && ja.w <= 8 && ja.w == jb.w && ja.h == jb.h && ja.x == jb.x && ja.y == jb.y &&
                 ja.rec == jb.rec && ja.hs == jb.hs && ja.vs == jb.vs && ja.dmvr == jb.dmvr && ja.hf_idx == jb.hf_idx &&
@@ -645,6 +641,51 @@ __global__ __launch_bounds__(256) void bipred_chroma_pair_kernel(const vvc355_bi
     }
 }
 
+// Chroma launch: one wave per EIGHT consecutive jobs, two waves per workgroup.  Four Cb/Cr pairs of 4:2:0 8x8 blocks whose windows
+// lie inside their planes are predicted together by chroma_quad (mc_chroma_quad.hpp); any other wave — the tail of the launch
+// included — does its pairs one after the other with chroma_pair.  The choice is wave-uniform.
+union ChromaLds {
+    BipredLds plain;
+    QuadLds quad;
+};
+
+template <int BD>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(5, 5))) void bipred_chroma_pair_kernel(const vvc355_bipred_job *__restrict__ jobs, int n_jobs)
+{
+    __shared__ __attribute__((aligned(16))) ChromaLds lds_all[2];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int ia = 8 * (xcd_chunked(blockIdx.x, gridDim.x) * 2 + wave);
+    if (ia >= n_jobs)
+        return;
+    ChromaLds &L = lds_all[wave];
+    if (ia + 8 <= n_jobs) {
+        // scalar look at the first descriptor: a wave of jobs of another shape declines before chroma_quad's 48 vector loads
+        const vvc355_bipred_job j0 = load_uniform(jobs + ia);
+        if (j0.w == 8 && j0.h == 8 && j0.hs == 1 && j0.vs == 1 && j0.chroma && j0.pred_flag != 1 && j0.pred_flag != 2 &&
+            chroma_quad<BD>(jobs, ia, L.quad, lane))
+            return;
+    }
+    const int end = min(ia + 8, n_jobs);
+#pragma unroll 1
+    for (int i = ia; i < end; i += 2) {
+        chroma_pair<BD>(jobs, i, n_jobs, L.plain, lane);
+        wave_sync();
+    }
+}
+
+// The launch for job arrays that cannot take the quad path, e.g. the 4x4 chroma blocks of affine coding units: one wave per pair,
+// four per workgroup, the one-pair path's 2.9 KB of LDS per wave and its registers only, so its occupancy is not the quad path's.
+template <int BD>
+__global__ __launch_bounds__(256) void bipred_chroma_one_pair_kernel(const vvc355_bipred_job *__restrict__ jobs, int n_jobs)
+{
+    __shared__ __attribute__((aligned(16))) BipredLds lds_all[4];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int ia = 2 * (xcd_chunked(blockIdx.x, gridDim.x) * 4 + wave);
+    if (ia >= n_jobs)
+        return;
+    chroma_pair<BD>(jobs, ia, n_jobs, lds_all[wave], lane);
+}
+
 // The inter half of combined inter / intra coding units (vvc355_ciip_frame_pass): one wave per job, luma and chroma tiles of a
 // picture in one launch.  CIIP has neither DMVR nor BDOF, so every job takes bipred_plain and a wave needs only the plain path's
 // LDS.  A job with w == 0 or h == 0 does nothing: the builder leaves such jobs in the slots of the records it rejects.
@@ -692,13 +733,22 @@ extern "C" void vvc355_bipred_chroma_batch(void *stream, int bd, const vvc355_bi
 {
     using namespace vvc355;
     if (n_jobs <= 0) return;
-    const int n_pairs = (n_jobs + 1) / 2;
-    VVC355_BD_DISPATCH(bd, hipLaunchKernelGGL((bipred_chroma_pair_kernel<BD>), dim3((n_pairs + 3) / 4), dim3(256), 0, (hipStream_t)stream, jobs_dev, n_jobs));
+    const int n_waves = (n_jobs + 7) / 8;             // eight jobs (four Cb/Cr pairs) per wave
+    VVC355_BD_DISPATCH(bd, hipLaunchKernelGGL((bipred_chroma_pair_kernel<BD>), dim3((n_waves + 1) / 2), dim3(128), 0, (hipStream_t)stream, jobs_dev, n_jobs));
     HIP_CHECK(hipGetLastError());
 }
 
 // the launch of ciip_pred_kernel for inter_cu.hip's vvc355_ciip_frame_pass (the kernel lives here, next to bipred_plain)
 namespace vvc355 {
+
+// chroma jobs that are known not to be 4:2:0 8x8 pairs (inter_cu.hip's affine pass writes 4x4 blocks): bipred_chroma_one_pair_kernel
+void chroma_pairs_launch(hipStream_t stream, int bd, const vvc355_bipred_job *jobs_dev, int n_jobs)
+{
+    if (n_jobs <= 0) return;
+    const int n_pairs = (n_jobs + 1) / 2;
+    VVC355_BD_DISPATCH(bd, hipLaunchKernelGGL((bipred_chroma_one_pair_kernel<BD>), dim3((n_pairs + 3) / 4), dim3(256), 0, stream, jobs_dev, n_jobs));
+    HIP_CHECK(hipGetLastError());
+}
 
 void ciip_pred_launch(hipStream_t stream, int bd, const vvc355_bipred_job *jobs_dev, int n_jobs)
 {
