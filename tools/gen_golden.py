@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/ref_slots.json and tests/golden/ref_passes.json: SHA-256 digests of what the reference's own C path computes
-on the case lists of tests/ref_cases.py, and of what its in-loop filter callers compute on the pictures of tests/ref_pass_cases.py.
+"""Regenerate tests/golden/ref_slots.json, tests/golden/ref_passes.json and tests/golden/ref_inter.json: SHA-256 digests of what the
+reference's own C path computes on the case lists of tests/ref_cases.py, of what its in-loop filter callers compute on the pictures of
+tests/ref_pass_cases.py, and of what its inter prediction callers compute on the pictures of tests/ref_inter_cases.py.
 
 Needs oracle/_ref/libvvcref.so (`make -C oracle ref`, or __graft_entry__.build() where the reference tree is present).
 For every group of at most 64 cases (slot, bit depth, table indices) the file holds [digest of the concatenated inputs,
 digest of the concatenated outputs]; it holds no samples.  A regeneration may only add slots and groups: a recorded digest that
 would change is an error (the case generator drifted, or the reference did), unless --replace says that the change is meant.
 ref_passes.json holds per picture one digest of the inputs, one per output table and one per plane after each stage, under the same rule.
+ref_inter.json holds per picture one digest of the inputs and one per output plane; regular pictures add tab_dmvr_mvf, CIIP pictures the
+scratch, the intra weights and the patched .joint bytes; same rule.  Its digests are layout-independent: planes cropped to their width,
+MvField entries with the pad bytes zeroed.
 Usage: python tools/gen_golden.py [--check | --replace]"""
 import hashlib
 import json
@@ -28,6 +32,11 @@ try:                  # ... or no whole-picture passes yet (ref_passes.json is t
     import ref_pass_cases  # noqa: E402
 except ImportError:
     ref_pass_cases = None
+
+try:                  # ... or no inter prediction pictures yet (ref_inter.json is then left alone)
+    import ref_inter_cases  # noqa: E402
+except ImportError:
+    ref_inter_cases = None
 
 CONTEXT_SLOTS_AFTER = "ilfnst_transform"          # the context slots follow vvc_intra.c's static functions in the file
 
@@ -110,6 +119,16 @@ def dumps_passes(doc):
     return "\n".join(lines)
 
 
+def generate_inter(lib):
+    """The document of ref_inter.json: the reference's whole-picture inter prediction runs (oracle/ref_shim_inter.c); nothing of the oracle's
+    enters the file."""
+    return {"source": "reference inter prediction callers (ff_vvc_predict_inter, ff_vvc_predict_ciip) through oracle/ref_shim_inter.c on "
+                      "tests/ref_inter_cases.py",
+            "format": "pictures[name][key] = sha256: inputs; the planes after prediction (p + component); dmvr = tab_dmvr_mvf, pad bytes zeroed; "
+                      "CIIP: scratch, weights (int32 [unit][3]), joint (the command array's .joint bytes after the patch)",
+            "pictures": {name: ref_inter_cases.host_digests(lib, "ref", name) for name in ref_inter_cases.picture_names()}}
+
+
 def changed_digests(old, new):
     """Groups of `old` that `new` drops or records differently: [] when `new` only adds to `old`."""
     return [f"{slot}/{key}" for slot, grp in old.items() for key, rec in grp.items() if new.get(slot, {}).get(key) != rec]
@@ -122,15 +141,23 @@ def main():
     text = dumps(generate(lib, "ref_"))
     passes = dumps_passes(generate_passes(lib, ref_lib.load_oracle()))
     p_path = ref_pass_cases.GOLDEN_PATH
+    inter = dumps_passes(generate_inter(lib)) if ref_inter_cases is not None else None
+    i_path = ref_inter_cases.GOLDEN_PATH if ref_inter_cases is not None else None
     if "--check" in sys.argv:
-        with open(PATH) as f:
-            if f.read() != text:
-                sys.exit("tests/golden/ref_slots.json is stale")
-        with open(p_path) as f:
-            sys.exit(0 if f.read() == passes else "tests/golden/ref_passes.json is stale")
+        for path, want in ((PATH, text), (p_path, passes), (i_path, inter)):
+            if path is None:
+                continue
+            if not os.path.exists(path):
+                sys.exit(f"{os.path.relpath(path, ROOT)} is missing")
+            with open(path) as f:
+                if f.read() != want:
+                    sys.exit(f"{os.path.relpath(path, ROOT)} is stale")
+        sys.exit(0)
     if "--replace" not in sys.argv:
         bad = changed_digests(ref_lib.load_golden(), json.loads(text)["slots"]) if os.path.exists(PATH) else []
         bad += changed_digests(ref_pass_cases.load_golden(), json.loads(passes)["pictures"]) if os.path.exists(p_path) else []
+        if i_path and os.path.exists(i_path):
+            bad += changed_digests(ref_inter_cases.load_golden(), json.loads(inter)["pictures"])
         if bad:
             sys.exit(f"{len(bad)} recorded groups would change or vanish (first: {bad[:4]}): nothing written; --replace if that is meant")
     with open(PATH, "w") as f:
@@ -140,6 +167,10 @@ def main():
     with open(p_path, "w") as f:
         f.write(passes)
     print(f"wrote {p_path}: {len(json.loads(passes)['pictures'])} pictures, {len(passes)} bytes")
+    if i_path:
+        with open(i_path, "w") as f:
+            f.write(inter)
+        print(f"wrote {i_path}: {len(json.loads(inter)['pictures'])} pictures, {len(inter)} bytes")
 
 
 if __name__ == "__main__":
