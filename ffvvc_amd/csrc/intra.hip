@@ -223,6 +223,10 @@ struct LTabs {
     __device__ __forceinline__ uint32_t filt4(int e) const { return t->luma_filter[e]; }
     __device__ __forceinline__ const uint8_t *mip(int size_id) const { return size_id == 0 ? t->mip4 : size_id == 1 ? t->mip8 : t->mip16; }
 };
+struct LTabsLane {                       // the same LDS copy read per lane (the planner: every lane has its own mode)
+    const IntraTabsLds *t;
+    __device__ __forceinline__ uint32_t angle_inv(int aidx) const { return t->angle_inv[aidx]; }
+};
 
 // ------------------------------------------------------------------------------------------------ leaf predictors
 // Executed by a group of NT lanes (a wave or the whole workgroup); `tid` is the lane's index in its group.
@@ -399,9 +403,9 @@ __device__ void pred_simple_k(int tid, PX src, int stride, R top, R left, int w,
     }
 }
 template <int BD, int NT, int V, typename R, typename PX>
-__device__ void pred_simple_q(int tid, PX src, int stride, R top, R left, int w, int h, int kind, int dc, bool pdpc)
+__device__ void pred_simple_q(int tid, PX src, int stride, R top, R left, int w, int h, int variant, int dc)        // variant = kind * 2 + pdpc
 {
-    switch (kind * 2 + (pdpc ? 1 : 0)) {
+    switch (variant) {
     case 0: pred_simple_k<BD, NT, V, 0, false>(tid, src, stride, top, left, w, h, dc); break;
     case 1: pred_simple_k<BD, NT, V, 0, true>(tid, src, stride, top, left, w, h, dc); break;
     case 2: pred_simple_k<BD, NT, V, 1, false>(tid, src, stride, top, left, w, h, dc); break;
@@ -480,11 +484,11 @@ __device__ void pred_angular_k(int tid, PX src, int stride, R top, R left, int w
     }
 }
 template <int BD, int NT, int V, typename R, typename PX, typename TB>
-__device__ void pred_angular_q(int tid, PX src, int stride, R top, R left, int w, int h, bool vertical,
-                               int c_idx, int angle, int inv, int nscale, int ref_idx, int filter_flag, int need_pdpc, TB tabs)
+__device__ void pred_angular_q(int tid, PX src, int stride, R top, R left, int w, int h, int variant,           // vertical * 4 + luma * 2 + pdpc
+                               int angle, int inv, int nscale, int ref_idx, int filter_flag, TB tabs)
 {
 #define VVC355_ANG(VERT, LUMA, PDPC) pred_angular_k<BD, NT, V, VERT, LUMA, PDPC>(tid, src, stride, top, left, w, h, angle, inv, nscale, ref_idx, filter_flag, tabs)
-    switch ((vertical ? 4 : 0) + (c_idx == 0 ? 2 : 0) + (need_pdpc ? 1 : 0)) {
+    switch (variant) {
     case 0: VVC355_ANG(false, false, false); break;
     case 1: VVC355_ANG(false, false, true); break;
     case 2: VVC355_ANG(false, true, false); break;
@@ -591,16 +595,41 @@ __global__ __launch_bounds__(256) void intra_leaf_kernel(LeafArgs a)
 // vvc_intra_template.c:467-592 (edge preparation) + :595-683 (dispatch, PDPC); one workgroup per job.
 // NT = 32: half a wave per block (w*h <= 64), eight blocks per workgroup; NT = 64: one wave per block (w*h <= 256), four per
 // workgroup; both with wave-level synchronisation only.  NT = 256: one workgroup per block.
-// the whole slot for one block, executed by a group of NT lanes (tid = lane's index in the group); arr = four edge arrays in LDS
-// plane = accessor of the component plane's sample (0, 0); stride in pixels
-template <int BD, int NT, typename PX, typename TB = GTabs>
-__device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_px, uint16_t (*arr)[kEdgeLen], int *scratch, int tid,
-                                const StripRef sr = kNoStrip, TB tabs = TB{})
+//
+// The slot in two halves.  intra_pred_setup: everything that depends on the job alone and on no sample — angle and inverse angle,
+// PDPC, the reference filter, the lengths of the reference arrays, the 4-tap filter choice and which predictor variant runs.
+// intra_pred_run: the samples — gather, smoothing, projection, predictor.  The flat entries call one after the other; the RECON
+// stage driver runs the set-up once per command, one command per lane, when it loads a window of commands (recon_plan.hpp), and
+// its walk calls intra_pred_run alone.
+struct IntraSetup {
+    int src_off;                         // the block's sample (0, 0) from the plane accessor's origin, in pixels
+    int x, w, h, c_idx, mode, ref_idx;   // x in component samples (the strip is addressed by picture column); mode after the wide-angle mapping
+    int angle, inv, nscale, need_pdpc, filter_flag;
+    int ref_line, left_size, top_size, uleft, utop, refw, refh, la, ta;
+    int mip_mode, variant;               // variant: pred_angular_q's case for a directional mode, pred_simple_q's otherwise
+    bool is_mip, mip_transposed, directional, smooth, cand_up_left, quads;
+};
+struct HTabs {      // the set-up's table accessor on the host
+    __host__ __device__ uint32_t angle_inv(int aidx) const { return intra_angle_entry(aidx); }
+};
+// four samples per lane once one-per-lane would take three or more steps of the nt lanes (the wave's time is its longest lane's instruction
+// count) and the block has whole groups of four along the store direction; one sample per lane otherwise.  PDPC is applied before the store.
+__host__ __device__ inline bool intra_quads(int nt, int w, int h, bool directional, int mode)
 {
-    const int stride = stride_px;
+    return w * h > 2 * nt && w >= 4 && (!directional || mode >= 34 || h >= 4);
+}
+__host__ __device__ inline int imin_(int a, int b) { return a < b ? a : b; }
+__host__ __device__ inline int imax_(int a, int b) { return a > b ? a : b; }
+// NT: lanes per block (decides `quads`); stride in pixels; tabs: angle_inv(aidx) of the lane's own index
+template <int NT, typename TB>
+__host__ __device__ inline IntraSetup intra_pred_setup(const vvc355_intra_job &j, int stride, TB tabs)
+{
+    IntraSetup s;
     const int w = j.w, h = j.h, c_idx = j.c_idx, mode = j.mode, ref_idx = j.ref_idx;
     const bool is_mip = j.is_mip, no_isp = !j.isp_split;
-    const PX src = plane.at(__mul24(j.y, stride) + j.x);
+    s.src_off = j.y * stride + j.x;
+    s.x = j.x; s.w = w; s.h = h; s.c_idx = c_idx; s.mode = mode; s.ref_idx = ref_idx;
+    s.is_mip = is_mip; s.mip_mode = j.mip_mode; s.mip_transposed = j.mip_transposed != 0; s.cand_up_left = j.cand_up_left != 0;
     const bool directional = !is_mip && mode != 0 && mode != 1 && mode != 50 && mode != 18;
     int angle = 0, inv = 0, nscale = 0, need_pdpc = 0;
     if (directional) {
@@ -611,15 +640,12 @@ __device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_
         if (!directional)
             need_pdpc = 1;
         else if (!(mode > 18 && mode < 50)) {
-            nscale = min(2, ilog2i(mode >= 50 ? h : w) - ilog2i(3 * inv - 2) + 8);
+            nscale = imin_(2, ilog2i(mode >= 50 ? h : w) - ilog2i(3 * inv - 2) + 8);
             need_pdpc = nscale >= 0;
         }
     }
-    uint16_t *left = arr[0] + kEdgeOrg, *top = arr[1] + kEdgeOrg, *fleft = arr[2] + kEdgeOrg, *ftop = arr[3] + kEdgeOrg;
-
     const bool rff = is_mip ? false : ref_filter_mode(mode);
     const bool smooth = !ref_idx && w * h > 32 && !c_idx && no_isp && rff;
-    const int ref_line = ref_idx == 3 ? -4 : -1 - ref_idx;
     int left_size, top_size, uleft, utop, refw = 0, refh = 0;
     if (is_mip || mode == 0)      { left_size = h + 1; top_size = w + 1; uleft = left_size + smooth; utop = top_size + smooth; }
     else if (mode == 1)           { uleft = left_size = h; utop = top_size = w; }
@@ -629,7 +655,37 @@ __device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_
         if (no_isp || c_idx) { refw = w * 2; refh = h * 2; } else { refw = j.cb_width + w; refh = j.cb_height + h; }
         utop = top_size = refw; uleft = left_size = refh;
     }
-    const int la = min(uleft, (int)j.left_avail), ta = min(utop, (int)j.top_avail);
+    int filter_flag = 0;
+    if (directional && !(rff || ref_idx || !no_isp)) {
+        const int ti = imax_(0, ((ilog2i(w) + ilog2i(h)) >> 1) - 2);           // thresholds 24, 14, 2, 0, 0
+        const int d50 = mode > 50 ? mode - 50 : 50 - mode, d18 = mode > 18 ? mode - 18 : 18 - mode;
+        filter_flag = imin_(d50, d18) > intra_filter_thres(ti);
+    }
+    s.directional = directional; s.angle = angle; s.inv = inv; s.nscale = nscale; s.need_pdpc = need_pdpc; s.filter_flag = filter_flag;
+    s.smooth = smooth;
+    s.ref_line = ref_idx == 3 ? -4 : -1 - ref_idx;
+    s.left_size = left_size; s.top_size = top_size; s.uleft = uleft; s.utop = utop; s.refw = refw; s.refh = refh;
+    s.la = imin_(uleft, (int)j.left_avail); s.ta = imin_(utop, (int)j.top_avail);
+    s.quads = intra_quads(NT, w, h, directional, mode);
+    if (directional)
+        s.variant = (mode >= 34 ? 4 : 0) + (c_idx == 0 ? 2 : 0) + (need_pdpc ? 1 : 0);
+    else
+        s.variant = (mode == 0 ? 0 : mode == 1 ? 1 : mode == 50 ? 2 : 3) * 2 + (need_pdpc ? 1 : 0);
+    return s;
+}
+
+// the samples' half of the slot, executed by a group of NT lanes (tid = lane's index in the group); arr = four edge arrays in LDS
+// plane = accessor of the component plane's sample (0, 0); stride in pixels
+template <int BD, int NT, typename PX, typename TB = GTabs>
+__device__ void intra_pred_run(const IntraSetup &s, PX plane, int stride, uint16_t (*arr)[kEdgeLen], int *scratch, int tid,
+                               const StripRef sr = kNoStrip, TB tabs = TB{})
+{
+    const int w = s.w, h = s.h, c_idx = s.c_idx, mode = s.mode, ref_idx = s.ref_idx;
+    const bool is_mip = s.is_mip, directional = s.directional, smooth = s.smooth, quads = s.quads;
+    const int angle = s.angle, inv = s.inv, nscale = s.nscale, filter_flag = s.filter_flag;
+    const int ref_line = s.ref_line, left_size = s.left_size, uleft = s.uleft, utop = s.utop, refw = s.refw, refh = s.refh, la = s.la, ta = s.ta;
+    const PX src = plane.at(s.src_off);
+    uint16_t *left = arr[0] + kEdgeOrg, *top = arr[1] + kEdgeOrg, *fleft = arr[2] + kEdgeOrg, *ftop = arr[3] + kEdgeOrg;
     const int prof_o = c_idx ? 32 : 0; (void)prof_o;
     unsigned long long t_ph = RPROF_NOW();
 #define RPHASE(slot) do { RPROF_ADD((slot) + prof_o, t_ph); t_ph = RPROF_NOW(); } while (0)
@@ -647,7 +703,7 @@ __device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_
             const int ie = i >= 0 ? min(i, avail - 1) : i;            // -1 past the end of an empty side: the corner
             int sx, sy;
             bool grey = false;
-            if (ie >= 0 || j.cand_up_left) {
+            if (ie >= 0 || s.cand_up_left) {
                 sx = is_top ? ie : ref_line; sy = is_top ? ref_line : ie;
             } else if (la) {
                 sx = ref_line; sy = 0;
@@ -658,13 +714,13 @@ __device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_
             }
             int v = mid;
             if (!grey)
-                v = (sr.on && sy < 0) ? sr.at(j.x + sx, sy) : src.ld(sx + __mul24(stride, sy));
+                v = (sr.on && sy < 0) ? sr.at(s.x + sx, sy) : src.ld(sx + __mul24(stride, sy));
             (is_top ? top : left)[i] = (uint16_t)v;
         }
     }
     group_sync<NT>();
     RPHASE(22);
-    if (rff && smooth) {                                  // ref_filter (:450)
+    if (smooth) {                                         // ref_filter (:450); smooth implies the mode's filter flag
         const int keep_last = left_size == uleft;
         if (tid == 0)
             fleft[-1] = ftop[-1] = (uint16_t)((left[0] + 2 * left[-1] + top[0] + 2) >> 2);
@@ -674,13 +730,7 @@ __device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_
         group_sync<NT>();
         left = fleft; top = ftop;
     }
-    int filter_flag = 0;
     if (directional) {
-        if (!(rff || ref_idx || !no_isp)) {
-            const int ti = max(0, ((ilog2i(w) + ilog2i(h)) >> 1) - 2);           // thresholds 24, 14, 2, 0, 0
-            const int dist = min(abs(mode - 50), abs(mode - 18));
-            filter_flag = dist > intra_filter_thres(ti);
-        }
         if (mode >= 34) {
             if (angle < 0) {
                 uint16_t *p = top - (ref_idx + 1);
@@ -706,16 +756,13 @@ __device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_
     RPHASE(23);
     LRef T{ top }, L{ left };
     if (is_mip) {
-        pred_mip<BD, NT>(tid, src, stride, T, L, w, h, j.mip_mode, j.mip_transposed, scratch, tabs);
+        pred_mip<BD, NT>(tid, src, stride, T, L, w, h, s.mip_mode, s.mip_transposed, scratch, tabs);
         RPHASE(24);
         return;
     }
-    // four samples per lane once one-per-lane would take three or more steps (the wave's time is its longest lane's instruction count) and the
-    // block has whole groups of four along the store direction; one sample per lane otherwise.  PDPC is applied before the store.
-    const bool quads = w * h > 2 * NT && w >= 4 && (!directional || mode >= 34 || h >= 4);
     if (directional) {
-        if (quads) pred_angular_q<BD, NT, 4>(tid, src, stride, T, L, w, h, mode >= 34, c_idx, angle, inv, nscale, ref_idx, filter_flag, need_pdpc, tabs);
-        else       pred_angular_q<BD, NT, 1>(tid, src, stride, T, L, w, h, mode >= 34, c_idx, angle, inv, nscale, ref_idx, filter_flag, need_pdpc, tabs);
+        if (quads) pred_angular_q<BD, NT, 4>(tid, src, stride, T, L, w, h, s.variant, angle, inv, nscale, ref_idx, filter_flag, tabs);
+        else       pred_angular_q<BD, NT, 1>(tid, src, stride, T, L, w, h, s.variant, angle, inv, nscale, ref_idx, filter_flag, tabs);
     } else {
         int dc = 0;
         if (mode == 1) {
@@ -725,16 +772,25 @@ __device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_
             const unsigned offset = w == h ? (unsigned)w << 1 : (unsigned)max(w, h);
             dc = (group_sum<NT>(part, tid, scratch) + (int)(offset >> 1)) >> ilog2i((int)offset);
         }
-        const int kind = mode == 0 ? 0 : mode == 1 ? 1 : mode == 50 ? 2 : 3;
+        const int kind = s.variant >> 1;
         // DC and horizontal stores cover whole groups of four columns (:856, :885): blocks narrower than four take the leaf routines
         if (w < 4 && (kind == 1 || kind == 3)) {
             if (kind == 1) pred_dc<BD, NT>(tid, src, stride, T, L, w, h, scratch);
             else           pred_vh<BD, NT>(tid, src, stride, L, w, h, false);
-        } else if (quads) pred_simple_q<BD, NT, 4>(tid, src, stride, T, L, w, h, kind, dc, need_pdpc != 0);
-        else              pred_simple_q<BD, NT, 1>(tid, src, stride, T, L, w, h, kind, dc, need_pdpc != 0);
+        } else if (quads) pred_simple_q<BD, NT, 4>(tid, src, stride, T, L, w, h, s.variant, dc);
+        else              pred_simple_q<BD, NT, 1>(tid, src, stride, T, L, w, h, s.variant, dc);
     }
     RPHASE(24);
 #undef RPHASE
+}
+
+// the whole slot for one block: set-up, then the samples
+template <int BD, int NT, typename PX, typename TB = GTabs>
+__device__ void intra_pred_body(const vvc355_intra_job &j, PX plane, int stride_px, uint16_t (*arr)[kEdgeLen], int *scratch, int tid,
+                                const StripRef sr = kNoStrip, TB tabs = TB{})
+{
+    const IntraSetup s = intra_pred_setup<NT>(j, stride_px, tabs);
+    intra_pred_run<BD, NT>(s, plane, stride_px, arr, scratch, tid, sr, tabs);
 }
 
 template <int BD, int NT>
@@ -1499,6 +1555,9 @@ __host__ __device__ inline int wide_angle_mode(int isp_split, int c_idx, int tb_
     return mode;
 }
 
+} // namespace vvc355
+#include "recon_plan.hpp"
+namespace vvc355 {
 
 static constexpr int kReconFlags = 16;
 #define VVC355_LDS __attribute__((address_space(3)))
@@ -1805,7 +1864,9 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
     uint16_t (*arr)[kEdgeLen] = L.arr[role];
     const LTabs tabs{ &L.tabs };
     VVC355_LDS uint32_t *cbuf = (VVC355_LDS uint32_t *)L.cmdbuf[role];
-    auto load_window = [&](uint32_t base, uint32_t *all_kinds) -> unsigned long long {
+    // plan (the walk's loads): every lane then plans its own command — one of this wave's — and writes the plan over the command's slot
+    // (recon_plan.hpp).  Which commands the wave takes is decided on the raw kinds, before that.
+    auto load_window = [&](uint32_t base, uint32_t *all_kinds, auto plan) -> unsigned long long {
         const uint32_t n_dw = min(64u, n_cmd - base) * CMD_DW;
         const uint32_t *g = (const uint32_t *)(cmds + base);
         uint32_t v[CMD_DW];
@@ -1818,7 +1879,32 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
         group_sync<64>();
         const uint32_t kinds = cbuf[tid * CMD_DW + 6];
         *all_kinds = kinds;
-        return __ballot(base + (uint32_t)tid < n_cmd && ((((kinds >> 16) & 0xff) > 0) == (role == 1)) && ((kinds >> 8) & 0xff) != VVC355_RECON_MARK);
+        const unsigned long long m = __ballot(base + (uint32_t)tid < n_cmd && ((((kinds >> 16) & 0xff) > 0) == (role == 1)) && ((kinds >> 8) & 0xff) != VVC355_RECON_MARK);
+        if constexpr (decltype(plan)::value) {
+            const bool mine = (m >> tid) & 1;
+            ReconPlan P;
+            if (mine) {
+                uint32_t q[CMD_DW], qn[CMD_DW] = {};
+#pragma unroll
+                for (int i = 0; i < CMD_DW; i++) q[i] = cbuf[tid * CMD_DW + i];
+                // the twin is the wave's next command, in this window (the compare the walk made per block, seven readlanes)
+                bool twin = false;
+                if (TILE && tid < 63 && ((m >> (tid + 1)) & 1)) {
+#pragma unroll
+                    for (int i = 2; i < 9; i++) qn[i] = cbuf[(tid + 1) * CMD_DW + i];
+                    twin = recon_plan_twin(q, qn);
+                }
+                const ReconPlanFrame pf = { f.hs, f.vs, f.ctb_log2, { ps0, ps1 }, TILE };
+                P = recon_plan(q, twin, pf, cx, LTabsLane{ &L.tabs });
+            }
+            group_sync<64>();                  // every lane has read its command and its neighbour's
+            if (mine) {
+#pragma unroll
+                for (int i = 0; i < CMD_DW; i++) cbuf[tid * CMD_DW + i] = P.d[i];
+            }
+            group_sync<64>();
+        }
+        return m;
     };
     // Availability pre-pass.  What ff_vvc_get_top_available / _left_available return for a block depends on the command list alone (the areas
     // the MARKs before it record), not on any sample — so it does not belong on the chain of dependent blocks.  Before waiting for the
@@ -1834,7 +1920,7 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
         uint32_t *cmd_dw = (uint32_t *)cmds;
         for (uint32_t base = 0; base < n_cmd; base += 64) {
             uint32_t kinds;
-            (void)load_window(base, &kinds);
+            (void)load_window(base, &kinds, std::false_type{});
             const uint32_t kind_l = (kinds >> 8) & 0xff, type_l = ((kinds >> 16) & 0xff) > 0;
             const bool in_l = base + (uint32_t)tid < n_cmd;
             const bool mine = type_l == (uint32_t)role;
@@ -1932,24 +2018,24 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
 #ifdef VVC355_RECON_PROF
     const long long c_loop = clock64();
 #endif
-    uint32_t win = 0, kinds_unused;
-    unsigned long long mask = load_window(0, &kinds_unused);
+    // The first advance() loads window 0: the window load, with its planner, has one call site in the walk (the loop's head, which a
+    // twin's second step goes through as well).
+    uint32_t win = (uint32_t)0 - 64u, kinds_unused;
+    unsigned long long mask = 0;
     auto advance = [&]() -> int {         // index of the wave's next command, -1 when its list is exhausted
         while (!mask) {
             if (win + 64 >= n_cmd)
                 return -1;
             win += 64;
-            mask = load_window(win, &kinds_unused);
+            mask = load_window(win, &kinds_unused, std::true_type{});
         }
         const int bit = __builtin_ctzll(mask);
         mask &= mask - 1;
         return (int)win + bit;
     };
     auto load_cmd = [&](int idx) -> uint32_t { return cbuf[(idx - (int)win) * CMD_DW + min(tid, CMD_DW - 1)]; };      // lane i holds dword i
-    int i0 = advance();
+    int i0 = -1;
     // luma_done = every luma command below this index is finished (the chroma wave waits on it before CCLM)
-    if (role == 0)
-        recon_luma_done_set(L, i0 >= 0 ? i0 : (int)n_cmd);
     auto shift = [&]() {
         i0 = advance();
         if (role == 0)
@@ -1958,134 +2044,106 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
     int4 pre[4] = {};                    // residuals fetched one command ahead (the first 1024 of the block)
     int pre_k = -1;
     int lmcs_xv = -1, lmcs_yv = -1, lmcs_scale = 0;      // lc->lmcs: the 64x64 unit whose chroma residual scale is known (reset per CTU, vvc_intra.c:509-510)
-    while (i0 >= 0) {
+    int n_shift = 1;                     // 2 after a Cb / Cr twin: its second command is done as well
+    for (;;) {
+        do shift(); while (--n_shift);
+        if (i0 < 0)
+            break;
+        n_shift = 1;
         const uint32_t k = (uint32_t)i0;
         const int i1 = mask ? (int)win + __builtin_ctzll(mask) : -1;        // the wave's next command, when this window holds it
         const uint32_t d0 = load_cmd(i0), d1 = i1 >= 0 ? load_cmd(i1) : 0u;
-        vvc355_recon_cmd c;
-        bool pair_next = false;
-        uint32_t avail_dw;                   // dword 9: the pre-pass's answers (left | top << 16)
-        {
-            uint32_t w[CMD_DW];
+        uint32_t p[CMD_DW];                  // the command's plan (recon_plan.hpp)
 #pragma unroll
-            for (int i = 0; i < CMD_DW; i++) w[i] = (uint32_t)__builtin_amdgcn_readlane((int)d0, i);
-            __builtin_memcpy(&c, w, sizeof(c));
-            avail_dw = w[9];
-            if (i1 >= 0) {
-                const uint32_t n6 = (uint32_t)__builtin_amdgcn_readlane((int)d1, 6);
-                // the wave's next command is a residual block: start its first loads now, so that they travel while this command
-                // (usually that block's prediction) runs — unless this command is about to use the registers they go to
-                if (((n6 >> 8) & 0xff) == VVC355_RECON_RESID && pre_k != i0) {
-                    const uint64_t ptr = (uint32_t)__builtin_amdgcn_readlane((int)d1, 0) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)d1, 1) << 32);
-                    const uint32_t wh = (uint32_t)__builtin_amdgcn_readlane((int)d1, 3);
-                    const int nn = (int)(wh & 0xffff) * (int)(wh >> 16);
+        for (int i = 0; i < CMD_DW; i++) p[i] = (uint32_t)__builtin_amdgcn_readlane((int)d0, i);
+        const int kind = (int)((p[6] >> 8) & 0xff);
+        if (i1 >= 0) {
+            const uint32_t n6 = (uint32_t)__builtin_amdgcn_readlane((int)d1, 6);
+            // the wave's next command is a residual block: start its first loads now, so that they travel while this command
+            // (usually that block's prediction) runs — unless this command is about to use the registers they go to
+            if (((n6 >> 8) & 0xff) == VVC355_RECON_RESID && pre_k != i0) {
+                const uint64_t ptr = (uint32_t)__builtin_amdgcn_readlane((int)d1, 0) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)d1, 1) << 32);
+                const uint32_t wh = (uint32_t)__builtin_amdgcn_readlane((int)d1, 3);
+                const int nn = (int)(wh & 0xffff) * (int)(wh >> 16);
 #pragma unroll
-                    for (int u = 0; u < 4; u++)
-                        if (tid * 4 + 256 * u < nn)
-                            pre[u] = gld<int4>((const int *)ptr + tid * 4 + 256 * u);
-                    pre_k = i1;
-                }
-                // Cb and Cr of a coding unit are predicted by two consecutive commands that differ in c_idx only (predict_intra,
-                // vvc_intra.c:263-264): when the next command is that twin, both go through one pass, half a wave each
-                if (TILE && c.kind == VVC355_RECON_PRED && c.c_idx == 1 && i1 == i0 + 1) {
-                    bool same = n6 == ((w[6] & ~0xff0000u) | 0x020000u);
-#pragma unroll
-                    for (int i = 2; i < 9; i++)
-                        if (i != 6)
-                            same = same && (uint32_t)__builtin_amdgcn_readlane((int)d1, i) == w[i];
-                    pair_next = same;
-                }
+                for (int u = 0; u < 4; u++)
+                    if (tid * 4 + 256 * u < nn)
+                        pre[u] = gld<int4>((const int *)ptr + tid * 4 + 256 * u);
+                pre_k = i1;
             }
         }
         const unsigned long long t_cmd = RPROF_NOW();
-        if (c.kind == VVC355_RECON_PRED) {
-            const int c_idx = c.c_idx, hs = c_idx ? f.hs : 0, vs = c_idx ? f.vs : 0;
-            const int x = c.x0 >> hs, y = c.y0 >> vs, w = c.w >> hs, h = c.h >> vs;
-            vvc355_intra_job j = {};
-            j.x = (int16_t)x; j.y = (int16_t)y; j.w = (int16_t)w; j.h = (int16_t)h;
-            j.mode = (int16_t)wide_angle_mode(c.isp_split, c_idx, w, h, c.cb_width, c.cb_height, c.mode);
-            j.cb_width = c.cb_width; j.cb_height = c.cb_height;
-            j.left_avail = (int16_t)(avail_dw & 0xffff);
-            j.top_avail = (int16_t)(avail_dw >> 16);
-            j.c_idx = (uint8_t)c_idx; j.ref_idx = c_idx ? 0 : c.ref_idx;
-            j.is_mip = c.is_mip; j.mip_mode = c.mip_mode; j.mip_transposed = c.mip_transposed;
-            j.isp_split = c.isp_split; j.bdpcm_flag = c.bdpcm_flag;
-            {   // ff_vvc_set_neighbour_available (vvc_ctu.c:2497-2510), luma coordinates
-                const int x0b = c.x0 & ctb_mask, y0b = c.y0 & ctb_mask;
-                const bool cand_up = cx.ctb_up || y0b, cand_left = cx.ctb_left || x0b;
-                j.cand_up_left = (x0b || y0b) ? (cand_left && cand_up) : cx.ctb_up_left;
-            }
-            const PX plane = pick3(c_idx, pl0, pl1, pl2);
-            StripRef sr = pick3(c_idx, st0, st1, st2);
-            sr.on = TILE && (y & ((ctb >> vs) - 1)) == 0;          // the block sits on the CTU's top edge: the rows above it are the strip
+        if (kind == VVC355_RECON_PRED) {
+            const IntraSetup su = recon_plan_setup(p);
+            const uint32_t fl = p[8] >> 16;
             RPROF_ADD(6 + 32 * role, t_cmd);
-            if constexpr (TILE) {
-                if (pair_next) {
-                    // lanes 0-31: Cb, lanes 32-63: Cr — same job, each half on its own tile, strip, edge arrays and scratch
+            if (TILE && (fl & kPlanTwin)) {
+                if constexpr (TILE) {
+                    // Cb and its twin Cr in one pass: lanes 0-31 Cb, lanes 32-63 Cr — same plan, each half on its own tile, strip, edge
+                    // arrays and scratch
                     const int half = tid >> 5;
                     const LPix plane2{ pl1.p, half ? pl2.base : pl1.base };
-                    StripRef sr2{ st1.p + (half ? (int)(st2.p - st1.p) : 0), st1.pitch, st1.x0s, sr.on };
-                    intra_pred_body<BD, 32>(j, plane2, ps1, L.arr[1 + half], L.scratch[1 + half], tid & 31, sr2, tabs);
+                    StripRef sr2{ st1.p + (half ? (int)(st2.p - st1.p) : 0), st1.pitch, st1.x0s, (fl & kPlanStrip) != 0 };
+                    intra_pred_run<BD, 32>(su, plane2, ps1, L.arr[1 + half], L.scratch[1 + half], tid & 31, sr2, tabs);
                     group_sync<64>();
-                    RPROF_ADD(9 + (int)c.kind + 32 * role, t_cmd);
-                    RPROF_INC(17 + (int)c.kind + 32 * role);
-                    shift();             // the twin is done as well
-                    shift();
-                    continue;
+                    n_shift = 2;
                 }
+            } else {
+                const PX plane = pick3(su.c_idx, pl0, pl1, pl2);
+                StripRef sr = pick3(su.c_idx, st0, st1, st2);
+                sr.on = (fl & kPlanStrip) != 0;
+                intra_pred_run<BD, 64>(su, plane, su.c_idx ? ps1 : ps0, arr, L.scratch[role], tid, sr, tabs);
+                if (TILE) group_sync<64>(); else recon_sync_mem();
             }
-            intra_pred_body<BD, 64>(j, plane, c_idx ? ps1 : ps0, arr, L.scratch[role], tid, sr, tabs);
-            if (TILE) group_sync<64>(); else recon_sync_mem();
-        } else if (c.kind == VVC355_RECON_CCLM) {
+        } else if (kind == VVC355_RECON_CCLM) {
             // the coding unit's luma (every luma command before this one) must be reconstructed
             while (recon_luma_done_get(L) < (int)k)
                 __builtin_amdgcn_s_sleep(1);
             group_sync<64>();
             vvc355_cclm_job j = {};
-            j.x0 = c.x0; j.y0 = c.y0; j.width = c.w; j.height = c.h;
-            j.top_avail_c = (int16_t)(avail_dw >> 16);
-            j.left_avail_c = (int16_t)(avail_dw & 0xffff);
-            j.mode = (uint8_t)c.mode; j.hs = f.hs; j.vs = f.vs;
-            j.avail_t = (uint8_t)((c.pad_[0] >> 1) & 1);
-            j.avail_l = (uint8_t)(c.pad_[0] & 1);
+            j.x0 = (int16_t)(p[2] & 0xffff); j.y0 = (int16_t)(p[2] >> 16); j.width = (int16_t)(p[3] & 0xffff); j.height = (int16_t)(p[3] >> 16);
+            j.top_avail_c = (int16_t)(p[9] >> 16);
+            j.left_avail_c = (int16_t)(p[9] & 0xffff);
+            j.mode = (uint8_t)(p[6] & 0xff); j.hs = f.hs; j.vs = f.vs;
+            j.avail_l = (uint8_t)(p[7] & 0xff);
+            j.avail_t = (uint8_t)((p[7] >> 8) & 0xff);
             j.collocated = f.collocated;
-            j.ctu_boundary = (c.y0 & ctb_mask) == 0;
+            j.ctu_boundary = (uint8_t)((p[7] >> 16) & 0xff);
             StripRef s0 = st0, s1 = st1, s2 = st2;
             s0.on = s1.on = s2.on = TILE && j.ctu_boundary;
             cclm_body<BD, 64>(j, pl0, ps0, pl1, pl2, ps1, ps1, L.prm[1], tid, s0, s1, s2);
             if (TILE) group_sync<64>(); else recon_sync_mem();
-        } else if (c.kind == VVC355_RECON_CIIP) {
+        } else if (kind == VVC355_RECON_CIIP) {
             // inter.put_ciip (vvc_inter_template.c:60) of a combined inter / intra block (pred_regular_luma / _chroma, vvc_inter.c:570-575,
             // :632-638): the intra prediction the previous command left in the picture, weighted against the inter prediction of the
-            // batched stage (c.resid: w x h pixels, packed rows); c.joint = ciip_derive_intra_weight (:530-548)
-            const int c_idx = c.c_idx, hs = c_idx ? f.hs : 0, vs = c_idx ? f.vs : 0, w = c.w >> hs, n = w * (c.h >> vs);
-            const int stride = c_idx ? ps1 : ps0, iw = c.joint;
-            const PX dst = pick3(c_idx, pl0, pl1, pl2).at((c.y0 >> vs) * stride + (c.x0 >> hs));
-            const uint8_t *inter = (const uint8_t *)c.resid;
-            const int lw = ilog2i(w);
+            // batched stage (resid: w x h pixels, packed rows); joint = ciip_derive_intra_weight (:530-548)
+            const int c_idx = (int)((p[4] >> 8) & 0xff), lw = (int)(p[4] & 0xff), w = 1 << lw, n = (int)p[5];
+            const int stride = c_idx ? ps1 : ps0, iw = (int)((p[4] >> 16) & 0xff);
+            const PX dst = pick3(c_idx, pl0, pl1, pl2).at((int)p[2]);
+            const uint8_t *inter = (const uint8_t *)(p[0] | ((uint64_t)p[1] << 32));
             for (int i = tid; i < n; i += 64) {
                 const int o = (i >> lw) * stride + (i & (w - 1));
                 dst.st(o, (dst.ld(o) * iw + ld_px<BD>(inter, i) * (4 - iw) + 2) >> 2);
             }
             if (TILE) group_sync<64>(); else recon_sync_mem();
         } else {
-            // RESID: itx.add_residual / add_residual_joint (vvcdsp_template.c:32,48) of the block the transform stage left in c.resid
-            const int c_idx = c.c_idx, hs = c_idx ? f.hs : 0, vs = c_idx ? f.vs : 0, w = c.w, n = w * c.h;
-            const int stride = c_idx ? ps1 : ps0;
-            const PX dst = pick3(c_idx, pl0, pl1, pl2).at((c.y0 >> vs) * stride + (c.x0 >> hs));
-            const int *res = (const int *)c.resid;
-            const int lw = ilog2i(w);
+            // RESID: itx.add_residual / add_residual_joint (vvcdsp_template.c:32,48) of the block the transform stage left in resid
+            const int c_idx = (int)((p[4] >> 8) & 0xff), lw = (int)(p[4] & 0xff), w = 1 << lw, n = (int)p[5];
+            const int stride = c_idx ? ps1 : ps0, joint = (int)((p[4] >> 16) & 0xff);
+            const PX dst = pick3(c_idx, pl0, pl1, pl2).at((int)p[2]);
+            const int *res = (const int *)(p[0] | ((uint64_t)p[1] << 32));
             const bool have = pre_k == (int)k;
-            const bool scaled = (c.joint & 8) != 0;
-            if (scaled && (lmcs_xv != (c.cu_x0 & ~(min(ctb, 64) - 1)) || lmcs_yv != (c.cu_y0 & ~(min(ctb, 64) - 1)))) {
+            const bool scaled = (p[4] >> 24) != 0;
+            const int xv = (int16_t)(p[7] & 0xffff), yv = (int16_t)(p[7] >> 16);       // the 64x64 unit of the coding unit
+            if (scaled && (lmcs_xv != xv || lmcs_yv != yv)) {
                 // lmcs_derive_chroma_scale (vvc_intra_template.c:390-429): average of the reconstructed luma left of and above the 64x64 unit of
                 // the coding unit.  Every luma command before this one must be done (the unit's neighbours may be this CTU's own blocks).
                 while (recon_luma_done_get(L) < (int)k)
                     __builtin_amdgcn_s_sleep(1);
                 group_sync<64>();
                 const int size_y = min(ctb, 64);
-                lmcs_xv = c.cu_x0 & ~(size_y - 1); lmcs_yv = c.cu_y0 & ~(size_y - 1);
-                const bool avail_t = (c.pad_[0] >> 1) & 1, avail_l = c.pad_[0] & 1;
+                lmcs_xv = xv; lmcs_yv = yv;
+                const bool avail_t = (p[8] >> 17) & 1, avail_l = (p[8] >> 16) & 1;
                 StripRef s0 = st0;
                 s0.on = TILE && (lmcs_yv & ctb_mask) == 0;
                 int v = 0;
@@ -2105,8 +2163,8 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
                 lmcs_scale = lmcs_scale_of_avg((const vvc355_lmcs_model *)f.lmcs_model, avg, tid);
             }
             auto resid_of = [&](int r) {                        // the joint sign / shift (pred_residual_joint), then lmcs_scale_chroma
-                if (c.joint & 1)
-                    r = (r * ((c.joint & 2) ? -1 : 1)) >> ((c.joint >> 2) & 1);
+                if (joint & 1)
+                    r = (r * ((joint & 2) ? -1 : 1)) >> ((joint >> 2) & 1);
                 if (scaled) {
                     const int v = clip_intp2(r, BD);
                     r = v > 0 ? (v * lmcs_scale + (1 << 10)) >> 11 : -((-v * lmcs_scale + (1 << 10)) >> 11);
@@ -2142,9 +2200,8 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
             }
             if (TILE) group_sync<64>(); else recon_sync_mem();
         }
-        RPROF_ADD(9 + (int)c.kind + 32 * role, t_cmd);
-        RPROF_INC(17 + (int)c.kind + 32 * role);
-        shift();
+        RPROF_ADD(9 + kind + 32 * role, t_cmd);
+        RPROF_INC(17 + kind + 32 * role);
     }
     RPROF_ADD(3 + 32 * role, t_loop);
 #ifdef VVC355_RECON_PROF
@@ -2275,6 +2332,23 @@ void vvc355_recon_prof_read(unsigned long long *out, int reset)
     }
 }
 #endif
+
+// HOST helper like vvc355_recon_order, no device work (tests/test_recon_plan_cpu.py): the plans the walk's window load makes of n
+// commands that one wave takes from one window, in order — cmds = ten dwords each, with the pre-pass's answers in place; ctx = ctb_up,
+// ctb_left, ctb_up_left, ox, oy of the CTU; plans = ten dwords each.  Layout: recon_plan.hpp.
+void vvc355_recon_plan_host(const uint32_t *cmds, int n, int hs, int vs, int ctb_log2, int pitch_luma, int pitch_chroma, int tile,
+                            const int *ctx, uint32_t *plans)
+{
+    using namespace vvc355;
+    const ReconPlanFrame pf = { hs, vs, ctb_log2, { pitch_luma, pitch_chroma }, tile != 0 };
+    const ReconCtx cx = { ctx[0], ctx[1], ctx[2], 0, ctx[3], ctx[4] };
+    for (int k = 0; k < n; k++) {
+        const uint32_t *q = cmds + 10 * (size_t)k;
+        const ReconPlan P = recon_plan(q, tile && k + 1 < n && recon_plan_twin(q, q + 10), pf, cx, HTabs{});
+        for (int i = 0; i < 10; i++)
+            plans[10 * (size_t)k + i] = P.d[i];
+    }
+}
 
 size_t vvc355_recon_state_bytes(int n_ctus) { return sizeof(int) * (size_t)(vvc355::kReconFlags + 2 * (n_ctus > 0 ? n_ctus : 0)); }
 
