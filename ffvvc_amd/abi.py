@@ -176,6 +176,9 @@ BATCH_SIGNATURES = {
     "deblock_qp_rec_pass": ("i", "ppp"),
     # inverse luma mapping of a whole picture from the per-CTB slice index and the per-slice flags (vvc355_lmcs_frame): no job array
     "lmcs_frame_pass":  ("i", "pipp"),
+    # a decoded picture's checksums where it lies (vvc355_pic_digest_frame): framecrc's Adler-32, the SEI's checksum and CRC per component
+    "pic_digest_work_bytes": ("z", "pi"),
+    "pic_digest_pass":  ("i", "pipp"),
     # is a ticket order one recon_frame_pass can run?  (host only)
     "recon_order_check": ("i", "piipi"),
     # every record-path stage of a picture in the documented order, validated as a whole before the first launch (vvc355_picture, HOST memory)
@@ -748,6 +751,26 @@ class LmcsFrame(ctypes.Structure):
 # what vvc355_lmcs_frame_pass returns for a frame it refuses (VVC355_LMCS_FRAME_E_*)
 (LMCS_FRAME_E_FRAME, LMCS_FRAME_E_BD, LMCS_FRAME_E_SIZE, LMCS_FRAME_E_CTB, LMCS_FRAME_E_GRID, LMCS_FRAME_E_STRIDE, LMCS_FRAME_E_COUNT,
  LMCS_FRAME_E_TABLES) = -1, -2, -3, -4, -5, -6, -7, -8
+
+# VVC355_DIGEST_*: the bits of vvc355_pic_digest_frame.what
+DIGEST_ADLER32, DIGEST_CHECKSUM, DIGEST_CRC = 1, 2, 4
+
+
+class PicDigestResult(ctypes.Structure):
+    """Mirror of vvc355_pic_digest_result."""
+    _fields_ = [("adler32", ctypes.c_uint32), ("plane_adler32", ctypes.c_uint32 * 3), ("checksum", ctypes.c_uint32 * 3),
+                ("crc", ctypes.c_uint16 * 3), ("n_comp", ctypes.c_uint16)]
+
+
+class PicDigestFrame(ctypes.Structure):
+    """Mirror of vvc355_pic_digest_frame."""
+    _fields_ = [("plane", ctypes.c_uint64 * 3), ("result", ctypes.c_uint64), ("work", ctypes.c_uint64), ("stride", ctypes.c_int32 * 3),
+                ("width", ctypes.c_int32 * 3), ("height", ctypes.c_int32 * 3), ("n_comp", ctypes.c_uint8), ("what", ctypes.c_uint8),
+                ("pad_", ctypes.c_uint8 * 2)]
+
+
+# what vvc355_pic_digest_pass returns for a frame it refuses (VVC355_PIC_DIGEST_E_*)
+(PIC_DIGEST_E_FRAME, PIC_DIGEST_E_BD, PIC_DIGEST_E_WHAT, PIC_DIGEST_E_SIZE, PIC_DIGEST_E_STRIDE, PIC_DIGEST_E_TABLES) = -1, -2, -3, -4, -5, -6
 
 # what vvc355_recon_order_check returns for an order it refuses (VVC355_RECON_ORDER_E_*)
 (RECON_ORDER_E_ARGS, RECON_ORDER_E_RANGE, RECON_ORDER_E_EMPTY, RECON_ORDER_E_DUPLICATE, RECON_ORDER_E_MISSING,

@@ -269,6 +269,61 @@ enum { VVC355_LMCS_FRAME_E_FRAME = -1, VVC355_LMCS_FRAME_E_BD = -2, VVC355_LMCS_
  * returns 0, or a negative VVC355_LMCS_FRAME_E_* with NOTHING launched */
 int vvc355_lmcs_frame_pass(void *stream, int bd, const vvc355_lmcs_frame *frame_dev, const vvc355_lmcs_frame *frame_host);
 
+/*
+ * The checksums of a decoded picture, computed where the picture lies: one streaming read of the planes gives the number the framecrc
+ * muxer prints for the picture and two of the three forms of the decoded picture hash SEI, so a host can check what was decoded without
+ * downloading it.  A host issues the pass on the picture's stream after vvc355_picture_pass (vvc355_picture itself does not carry it).
+ *
+ * The BYTES of component c are rows 0..height[c]-1 of its rectangle, each width[c] samples: one byte per sample at bd 8, two bytes, low
+ * byte first, at bd 10 and 12 — AS STORED: nothing is masked to the bit depth.  Pitch padding is never read.
+ *
+ *   adler32, plane_adler32[c]   zlib's Adler-32 (RFC 1950 §8.2) with start value 0 (A = 0, B = 0) instead of 1: what
+ *                       libavformat/framecrcenc.c:53 does, av_adler32_update(0, pkt->data, pkt->size).  `adler32` is over the bytes of
+ *                       components 0..n_comp-1 one after the other (the rawvideo payload of the picture: the planes without pitch),
+ *                       plane_adler32[c] over component c alone.
+ *   checksum[c]         dph_sei_picture_checksum[c] (Rec. ITU-T H.274 §8.8.2; HEVC §D.3.19, picture_checksum): sum = 0; for every sample
+ *                       s at (x, y) of the rectangle, mask = (x & 0xFF) ^ (y & 0xFF) ^ (x >> 8) ^ (y >> 8); sum += (s & 0xFF) ^ mask; above
+ *                       8 bit also sum += (s >> 8) ^ mask; modulo 2^32.
+ *   crc[c]              dph_sei_picture_crc[c] (same clauses): the bit-serial CRC with register 0xFFFF, polynomial 0x1021, most significant
+ *                       bit first, over the bytes of the component followed by 16 zero bits.  That is the direct-form CRC-CCITT with
+ *                       initial value 0x1D0F over the same bytes.
+ * The third form of the SEI, MD5, is not computed: it chains 64-byte blocks serially per component.
+ * Fields of the result that `what` does not ask for are written as 0, as are the entries of components beyond n_comp.
+ */
+enum { VVC355_DIGEST_ADLER32 = 1, VVC355_DIGEST_CHECKSUM = 2, VVC355_DIGEST_CRC = 4 };
+
+typedef struct vvc355_pic_digest_result {   /* 36 bytes, no implicit padding */
+    uint32_t adler32;           /* planes 0..n_comp-1 concatenated row by row without pitch, start value 0: framecrc's number */
+    uint32_t plane_adler32[3];  /* each plane alone, start value 0 */
+    uint32_t checksum[3];       /* decoded picture hash SEI, picture_checksum per component */
+    uint16_t crc[3];            /* decoded picture hash SEI, picture_crc per component */
+    uint16_t n_comp;
+} vvc355_pic_digest_result;
+
+typedef struct vvc355_pic_digest_frame {    /* 80 bytes, no implicit padding */
+    uint64_t plane[3];   /* DEVICE: first sample of each component's rectangle (the caller adds a crop offset); read only */
+    uint64_t result;     /* DEVICE vvc355_pic_digest_result, written whole */
+    uint64_t work;       /* DEVICE scratch of vvc355_pic_digest_work_bytes() bytes, one per call in flight */
+    int32_t  stride[3];  /* bytes */
+    int32_t  width[3], height[3];   /* samples, per component */
+    uint8_t  n_comp;     /* 1 (4:0:0) or 3 */
+    uint8_t  what;       /* VVC355_DIGEST_* bits; fields not asked for are written as 0 */
+    uint8_t  pad_[2];
+} vvc355_pic_digest_frame;
+/* what vvc355_pic_digest_pass returns for a frame it refuses, in this order: no frame, or n_comp not 1 or 3; bd not 8 / 10 / 12; `what` 0 or
+ * with bits above 7, or non-zero pad bytes; a width or height of a counted component <= 0 or beyond 65535; a stride smaller than a row, no
+ * multiple of the pixel size, 8 MiB or more, or a plane span (stride * height) of 2 GiB or more; a plane of a counted component, `result`
+ * or `work` missing (or a plane not aligned to the pixel size, `result` or `work` not aligned to 4 bytes) */
+enum { VVC355_PIC_DIGEST_E_FRAME = -1, VVC355_PIC_DIGEST_E_BD = -2, VVC355_PIC_DIGEST_E_WHAT = -3, VVC355_PIC_DIGEST_E_SIZE = -4,
+       VVC355_PIC_DIGEST_E_STRIDE = -5, VVC355_PIC_DIGEST_E_TABLES = -6 };
+/* bytes of frame.work for this frame (they depend on the sizes only, and stay below 128 KiB); 0 for a frame the pass would refuse, so a
+ * host that sizes the buffer before it has one puts any non-zero value into `work` for this call */
+size_t vvc355_pic_digest_work_bytes(const vvc355_pic_digest_frame *frame_host, int bd);
+/* Two launches on `stream`, the second a single workgroup: no host synchronisation, no allocation, no atomics; may be captured in a
+ * graph.  The host copy of the frame is checked before any HIP call.
+ * returns 0, or a negative VVC355_PIC_DIGEST_E_* with NOTHING launched */
+int vvc355_pic_digest_pass(void *stream, int bd, const vvc355_pic_digest_frame *frame_dev, const vvc355_pic_digest_frame *frame_host);
+
 /* VVCLMCSDSPContext.filter — vvcdsp.h:124, vvc_filter_template.c:25 */
 void vvc355_lmcs_filter(int bd, uint8_t *dst, ptrdiff_t dst_stride, int width, int height, const uint8_t *lut);
 /* VVCSAODSPContext.band_filter[*] — vvcdsp.h:138, h2656_sao_template.c:24 */
