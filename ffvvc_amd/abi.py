@@ -90,6 +90,9 @@ RUNTIME_SIGNATURES = {
     "upload":         ("v", "ppz"),
     "download":       ("v", "ppz"),
     "copy_async":     ("v", "pppz"),
+    "host_alloc":     ("p", "z"),
+    "host_free":      ("v", "p"),
+    "download_async": ("v", "pppz"),
     "stream_create":  ("p", ""),
     "stream_destroy": ("v", "p"),
     "stream_sync":    ("v", "p"),
@@ -179,6 +182,8 @@ BATCH_SIGNATURES = {
     # a decoded picture's checksums where it lies (vvc355_pic_digest_frame): framecrc's Adler-32, the SEI's checksum and CRC per component
     "pic_digest_work_bytes": ("z", "pi"),
     "pic_digest_pass":  ("i", "pipp"),
+    # the hand-over of a decoded picture (vvc355_pic_output_frame): crop and repack on the device, planar or semi-planar, as stored, 16 or 8 bit
+    "pic_output_pass":  ("i", "pipp"),
     # is a ticket order one recon_frame_pass can run?  (host only)
     "recon_order_check": ("i", "piipi"),
     # every record-path stage of a picture in the documented order, validated as a whole before the first launch (vvc355_picture, HOST memory)
@@ -771,6 +776,22 @@ class PicDigestFrame(ctypes.Structure):
 
 # what vvc355_pic_digest_pass returns for a frame it refuses (VVC355_PIC_DIGEST_E_*)
 (PIC_DIGEST_E_FRAME, PIC_DIGEST_E_BD, PIC_DIGEST_E_WHAT, PIC_DIGEST_E_SIZE, PIC_DIGEST_E_STRIDE, PIC_DIGEST_E_TABLES) = -1, -2, -3, -4, -5, -6
+
+# VVC355_OUT_*: vvc355_pic_output_frame.layout, and the bits of .flags
+OUT_PLANAR, OUT_SEMI = 0, 1
+OUT_SWAP_UV = 1
+
+
+class PicOutputFrame(ctypes.Structure):
+    """Mirror of vvc355_pic_output_frame."""
+    _fields_ = [("src", ctypes.c_uint64 * 3), ("dst", ctypes.c_uint64 * 3), ("src_stride", ctypes.c_int32 * 3), ("dst_stride", ctypes.c_int32 * 3),
+                ("width", ctypes.c_int32 * 3), ("height", ctypes.c_int32 * 3), ("n_comp", ctypes.c_uint8), ("layout", ctypes.c_uint8),
+                ("out_bits", ctypes.c_uint8), ("flags", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 4)]
+
+
+# what vvc355_pic_output_pass returns for a frame it refuses (VVC355_PIC_OUTPUT_E_*)
+(PIC_OUTPUT_E_FRAME, PIC_OUTPUT_E_BD, PIC_OUTPUT_E_FORMAT, PIC_OUTPUT_E_SIZE, PIC_OUTPUT_E_STRIDE, PIC_OUTPUT_E_PLANES,
+ PIC_OUTPUT_E_OVERLAP) = -1, -2, -3, -4, -5, -6, -7
 
 # what vvc355_recon_order_check returns for an order it refuses (VVC355_RECON_ORDER_E_*)
 (RECON_ORDER_E_ARGS, RECON_ORDER_E_RANGE, RECON_ORDER_E_EMPTY, RECON_ORDER_E_DUPLICATE, RECON_ORDER_E_MISSING,

@@ -40,6 +40,17 @@ void vvc355_copy_async(void *stream, void *dst_dev, const void *src_dev, size_t 
 {
     HIP_CHECK(hipMemcpyAsync(dst_dev, src_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
 }
+void *vvc355_host_alloc(size_t bytes)
+{
+    void *p = nullptr;
+    HIP_CHECK(hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault));
+    return p;
+}
+void vvc355_host_free(void *host) { HIP_CHECK(hipHostFree(host)); }
+void vvc355_download_async(void *stream, void *host, const void *dev, size_t bytes)
+{
+    HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+}
 void *vvc355_stream_create(void)
 {
     hipStream_t s;

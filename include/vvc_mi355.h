@@ -45,6 +45,12 @@ void  vvc355_free(void *dev);
 void  vvc355_upload(void *dev, const void *host, size_t bytes);
 void  vvc355_download(void *host, const void *dev, size_t bytes);
 void  vvc355_copy_async(void *stream, void *dst_dev, const void *src_dev, size_t bytes);   /* device to device, stream-ordered */
+/* Pinned host memory and the stream-ordered download into it: the copy is queued behind the work already on `stream` and the call returns
+ * at once; `host` holds the bytes after vvc355_stream_sync(stream) or an event recorded behind the copy.  `host` comes from
+ * vvc355_host_alloc (into pageable memory the runtime stages the copy and the call may block). */
+void *vvc355_host_alloc(size_t bytes);
+void  vvc355_host_free(void *host);
+void  vvc355_download_async(void *stream, void *host, const void *dev, size_t bytes);
 void *vvc355_stream_create(void);
 void  vvc355_stream_destroy(void *stream);
 void  vvc355_stream_sync(void *stream);          /* NULL = the default stream */
@@ -323,6 +329,51 @@ size_t vvc355_pic_digest_work_bytes(const vvc355_pic_digest_frame *frame_host, i
  * graph.  The host copy of the frame is checked before any HIP call.
  * returns 0, or a negative VVC355_PIC_DIGEST_E_* with NOTHING launched */
 int vvc355_pic_digest_pass(void *stream, int bd, const vvc355_pic_digest_frame *frame_dev, const vvc355_pic_digest_frame *frame_host);
+
+/*
+ * The hand-over of a decoded picture: crop, repack and (where asked) change the sample size of the planes where they lie, so that only
+ * the bytes a consumer wants leave the device.  The planes of a decoder are planar at a padded pitch, samples above 8 bit in the LOW bits
+ * of a uint16; the surfaces consumers take are planar without padding (yuv420p, yuv420p10le, ...) or semi-planar with the value in the
+ * HIGH bits (NV12 / NV16 / NV24, P010 / P210 / P410, P012 / P212 / P412: libavutil/pixdesc.c; the repack is what
+ * libswscale/swscale_unscaled.c:142-270 does on a host).  A host issues the pass on the picture's stream after vvc355_picture_pass, like the
+ * digest (vvc355_picture itself does not carry it), and vvc355_download_async() moves the packed bytes.
+ *
+ * S is the stored sample of the source: uint8 at bd 8, uint16, low byte first, at bd 10 and 12 — AS STORED: nothing is masked.
+ *   out_bits == bd            D = S, the sample size unchanged (yuv4xxp, yuv4xxp10le, yuv4xxp12le; NV12 / NV16 / NV24 at bd 8)
+ *   out_bits == 16, any bd    D = (S << (16 - bd)) & 0xFFFF, uint16, low byte first (the P010 / P012 family; swscale_unscaled.c:237-264)
+ *   out_bits == 8, bd 10 / 12 D = min((S + (1 << (bd - 9))) >> (bd - 8), 255), uint8 (rounded, not dithered; 1023 at 10 bit rounds to 256: clipped)
+ * VVC355_OUT_PLANAR: component c goes to dst[c].  VVC355_OUT_SEMI: n_comp is 3, width[1] == width[2], height[1] == height[2] and dst[2] is 0;
+ * luma goes to dst[0]; row y of dst[1] holds Cb(x, y) at sample index 2x and Cr(x, y) at 2x + 1, with VVC355_OUT_SWAP_UV the two exchanged
+ * (NV21, NV42); dst_stride[2] is not looked at.  VVC355_OUT_SWAP_UV is refused under VVC355_OUT_PLANAR (exchange dst[1] and dst[2]).
+ * In dst only the bytes of the rows are written: pitch padding and everything around the planes keep their bytes.  Nothing outside the
+ * source rectangles is read.
+ */
+enum { VVC355_OUT_PLANAR = 0, VVC355_OUT_SEMI = 1 };
+enum { VVC355_OUT_SWAP_UV = 1 };
+
+typedef struct vvc355_pic_output_frame {    /* 104 bytes, no implicit padding */
+    uint64_t src[3];         /* DEVICE: first sample of each component's rectangle (the caller adds the conformance window's offset); read only */
+    uint64_t dst[3];         /* DEVICE: first byte of each output plane */
+    int32_t  src_stride[3];  /* bytes */
+    int32_t  dst_stride[3];  /* bytes */
+    int32_t  width[3], height[3];   /* samples, per component */
+    uint8_t  n_comp;         /* 1 (4:0:0) or 3 */
+    uint8_t  layout;         /* VVC355_OUT_PLANAR or VVC355_OUT_SEMI */
+    uint8_t  out_bits;       /* bd, 16, or 8 */
+    uint8_t  flags;          /* VVC355_OUT_SWAP_UV */
+    uint8_t  pad_[4];        /* 0 */
+} vvc355_pic_output_frame;
+/* what vvc355_pic_output_pass returns for a frame it refuses, in this order: no frame, or n_comp not 1 or 3; bd not 8 / 10 / 12; a layout,
+ * out_bits or flags outside the above, non-zero pad bytes, or the conditions of VVC355_OUT_SEMI not met; a width or height of a component
+ * <= 0 or beyond 65535; a source or destination stride smaller than a row, no multiple of its sample size or 8 MiB or more, or a plane
+ * span (stride * height) of 2 GiB or more; a source or destination plane missing or not aligned to its sample size; a destination plane
+ * whose bytes (first row to the end of the last) overlap those of a source plane: the pass does not work in place */
+enum { VVC355_PIC_OUTPUT_E_FRAME = -1, VVC355_PIC_OUTPUT_E_BD = -2, VVC355_PIC_OUTPUT_E_FORMAT = -3, VVC355_PIC_OUTPUT_E_SIZE = -4,
+       VVC355_PIC_OUTPUT_E_STRIDE = -5, VVC355_PIC_OUTPUT_E_PLANES = -6, VVC355_PIC_OUTPUT_E_OVERLAP = -7 };
+/* One launch on `stream`: no host synchronisation, no allocation, no atomics; may be captured in a graph.  The host copy of the frame is
+ * checked before any HIP call.
+ * returns 0, or a negative VVC355_PIC_OUTPUT_E_* with NOTHING launched */
+int vvc355_pic_output_pass(void *stream, int bd, const vvc355_pic_output_frame *frame_dev, const vvc355_pic_output_frame *frame_host);
 
 /* VVCLMCSDSPContext.filter — vvcdsp.h:124, vvc_filter_template.c:25 */
 void vvc355_lmcs_filter(int bd, uint8_t *dst, ptrdiff_t dst_stride, int width, int height, const uint8_t *lut);
