@@ -184,6 +184,11 @@ BATCH_SIGNATURES = {
     "pic_digest_pass":  ("i", "pipp"),
     # the hand-over of a decoded picture (vvc355_pic_output_frame): crop and repack on the device, planar or semi-planar, as stored, 16 or 8 bit
     "pic_output_pass":  ("i", "pipp"),
+    # the hand-back of collocated motion (vvc355_col_mvf_frame): one packed 16-byte entry per 8x8 luma block, DMVR refinement overlaid from
+    # the inter stage's jobs and records; the two host helpers unpack an entry and put a picture's entries into a host MvField table
+    "col_mvf_pass":     ("i", "ppp"),
+    "col_mv_unpack":    ("v", "pppp"),
+    "col_mvf_scatter":  ("v", "piiipi"),
     # is a ticket order one recon_frame_pass can run?  (host only)
     "recon_order_check": ("i", "piipi"),
     # every record-path stage of a picture in the documented order, validated as a whole before the first launch (vvc355_picture, HOST memory)
@@ -792,6 +797,24 @@ class PicOutputFrame(ctypes.Structure):
 # what vvc355_pic_output_pass returns for a frame it refuses (VVC355_PIC_OUTPUT_E_*)
 (PIC_OUTPUT_E_FRAME, PIC_OUTPUT_E_BD, PIC_OUTPUT_E_FORMAT, PIC_OUTPUT_E_SIZE, PIC_OUTPUT_E_STRIDE, PIC_OUTPUT_E_PLANES,
  PIC_OUTPUT_E_OVERLAP) = -1, -2, -3, -4, -5, -6, -7
+
+COL_MVF_COMPRESS = 1                 # VVC355_COL_MVF_COMPRESS: vvc355_col_mvf_frame.flags bit 0
+
+
+class ColMv(ctypes.Structure):
+    """Mirror of vvc355_col_mv: [list][x, y]."""
+    _fields_ = [("w", (ctypes.c_uint32 * 2) * 2)]
+
+
+class ColMvfFrame(ctypes.Structure):
+    """Mirror of vvc355_col_mvf_frame."""
+    _fields_ = [("mvf", ctypes.c_uint64), ("col", ctypes.c_uint64), ("jobs_luma", ctypes.c_uint64), ("records", ctypes.c_uint64),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("mvf_stride", ctypes.c_int32), ("col_stride", ctypes.c_int32),
+                ("n_jobs", ctypes.c_int32), ("flags", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 3)]
+
+
+# what vvc355_col_mvf_pass returns for a frame it refuses (VVC355_COL_MVF_E_*)
+(COL_MVF_E_FRAME, COL_MVF_E_SIZE, COL_MVF_E_STRIDE, COL_MVF_E_TABLES, COL_MVF_E_JOBS, COL_MVF_E_FLAGS, COL_MVF_E_OVERLAP) = -1, -2, -3, -4, -5, -6, -7
 
 # what vvc355_recon_order_check returns for an order it refuses (VVC355_RECON_ORDER_E_*)
 (RECON_ORDER_E_ARGS, RECON_ORDER_E_RANGE, RECON_ORDER_E_EMPTY, RECON_ORDER_E_DUPLICATE, RECON_ORDER_E_MISSING,

@@ -375,6 +375,75 @@ enum { VVC355_PIC_OUTPUT_E_FRAME = -1, VVC355_PIC_OUTPUT_E_BD = -2, VVC355_PIC_O
  * returns 0, or a negative VVC355_PIC_OUTPUT_E_* with NOTHING launched */
 int vvc355_pic_output_pass(void *stream, int bd, const vvc355_pic_output_frame *frame_dev, const vvc355_pic_output_frame *frame_host);
 
+/*
+ * The hand-back of collocated motion: the third thing that leaves the device per picture, after the digest and the packed surface.
+ * vvc355_inter_frame_predict refines motion on the device (DMVR) and set_dmvr_info (vvc_inter.c:750-762) stores it in
+ * fc->ref->tab_dmvr_mvf, which the motion derivation of LATER pictures reads as collocated motion: temporal_luma_motion_vector
+ * (vvc_mvs.c:220-245) and sb_temproal_luma_motion (vvc_mvs.c:1016-1022).  Motion derivation is host work, so a parser bound to this
+ * backend needs that motion on the host.  It does not need the table: every read is at (x & ~7, y & ~7) (vvc_mvs.c:231-232, :241-242,
+ * :1001-1002), one entry in four; of the entry pred_flag, ref_idx[2] and mv[2] are used; and the vector goes through mv_compression
+ * (vvc_mvs.c:57-69, the temporal motion buffer compression of H.266 clause 8.5.2.15) before anything else (check_mvset, :104).  So the pass
+ * writes one 16-byte entry per 8x8 luma block: a sixth of the table (24 bytes per 4x4 block), moved by vvc355_download_async.
+ *
+ * Entry (gx, gy) of `col`, gx < ceil(width / 8), gy < ceil(height / 8), describes the MvField M at table position (row 2 * gy, column
+ * 2 * gx); width and height are multiples of 4, so that position exists.  For each list l, with used = (M.pred_flag >> l) & 1:
+ *   w[l][0] = used ? (M.mv[l][0] & 0x7FFFF) | (M.ref_idx[l] & 0x1F) << 19 : 0
+ *   w[l][1] = (used ? M.mv[l][1] & 0x7FFFF : 0) | (l == 0 ? (M.pred_flag & 3) << 19 : 0)
+ * An intra unit is sixteen zero bytes.  The entry is a function of what the reference reads and of nothing else: not of M's pad bytes,
+ * hpel_if_idx, bcw_idx, ciip_flag, nor of the stale motion and ref_idx of a list that is not used.
+ * With VVC355_COL_MVF_COMPRESS the stored vector is mv_compression(mv), per component (>> arithmetic, log2 = floor):
+ *   s = v >> 17; f = log2((v ^ s) | 31) - 4; v' = (v + ((1 << f) >> 2)) & ((-(1 << f)) >> 1)
+ * which lies in [-2^17, 2^17] and needs 19 bits signed: hence the field.  mv_compression is idempotent, so check_mvset run on vectors that
+ * are compressed already gives the same result bit for bit, and TAB_MVF reads of a table filled by vvc355_col_mvf_scatter work unchanged
+ * (tests/test_col_mvf_cpu.py proves the idempotence over the whole range).  Without the flag the vector is stored as it is; a component
+ * outside 19 bits signed is outside the contract (the reference clips motion to 18 bits wherever it makes it).
+ * Nothing outside the ceil(width / 8) entries of a row of `col` is written: col_stride padding and everything around the array keep
+ * their bytes.
+ *
+ * Where the refined motion comes from:
+ *   n_jobs == 0   `mvf` is taken as it is: a host that kept a full dmvr_mvf on the device passes that.
+ *   n_jobs > 0    `mvf` is the UNREFINED table (vvc355_inter_frame.mvf, dmvr_mvf = 0 there) and a second launch overlays the refinement:
+ *                 for each luma job i with dmvr != 0, every grid point inside its rectangle (x <= 8 * gx < x + w, likewise y) gets the
+ *                 vector of records[i].mv in the lists the entry uses, compressed when asked; the flags and ref_idx of the entry stay
+ *                 what the first launch wrote.  That is set_dmvr_info restricted to the entries anyone reads.  DMVR sub-blocks are 8 or
+ *                 16 wide and high and may start at x = 4 mod 8 (a unit behind a 4-wide neighbour), so a job covers one to four grid
+ *                 points; sub-blocks are disjoint, so no atomics.  A job whose rectangle is not 4-aligned, not 8 or 16 on a side, or
+ *                 reaches outside the picture is skipped: nothing is written for it.
+ * vvc355_picture does not carry the pass: like the digest and the output pass it is issued on the picture's stream, after
+ * vvc355_inter_frame_predict (or _pass, or vvc355_picture_pass) when it reads jobs and records.
+ */
+enum { VVC355_COL_MVF_COMPRESS = 1 };
+
+typedef struct vvc355_col_mv { uint32_t w[2][2]; } vvc355_col_mv;    /* 16 bytes: [list][x, y] */
+
+typedef struct vvc355_col_mvf_frame {     /* 56 bytes, no implicit padding */
+    uint64_t mvf;          /* DEVICE MvField[] (vvc355_mvfield, 24 bytes), mvf_stride entries per row: read only */
+    uint64_t col;          /* DEVICE vvc355_col_mv[], col_stride entries per row, ceil(height / 8) rows */
+    uint64_t jobs_luma, records;   /* 0, or vvc355_inter_frame.jobs_luma / .records as vvc355_inter_frame_predict left them */
+    int32_t  width, height;        /* luma samples */
+    int32_t  mvf_stride, col_stride, n_jobs;
+    uint8_t  flags;        /* VVC355_COL_MVF_COMPRESS = 1 */
+    uint8_t  pad_[3];      /* 0 */
+} vvc355_col_mvf_frame;
+/* what vvc355_col_mvf_pass returns for a frame it refuses, in this order: no frame; a width or height <= 0, no multiple of 4 or beyond
+ * 32764 (the jobs carry int16 positions); mvf_stride < width / 4, col_stride < ceil(width / 8), or a table span (stride * rows * entry
+ * size) of 2 GiB or more; `mvf` or `col` missing, or not aligned to 8 / 16 bytes; n_jobs < 0, or n_jobs > 0 with jobs_luma or records
+ * missing (or not aligned to 8 / 16 bytes); flag bits above 0, or non-zero pad bytes; the bytes of `col` (first entry to the last of the
+ * last row) overlapping those of `mvf` */
+enum { VVC355_COL_MVF_E_FRAME = -1, VVC355_COL_MVF_E_SIZE = -2, VVC355_COL_MVF_E_STRIDE = -3, VVC355_COL_MVF_E_TABLES = -4,
+       VVC355_COL_MVF_E_JOBS = -5, VVC355_COL_MVF_E_FLAGS = -6, VVC355_COL_MVF_E_OVERLAP = -7 };
+/* One launch on `stream`, two with n_jobs > 0: no host synchronisation, no allocation, no atomics; may be captured in a graph.  The host
+ * copy of the frame is checked before any HIP call.
+ * returns 0, or a negative VVC355_COL_MVF_E_* with NOTHING launched */
+int vvc355_col_mvf_pass(void *stream, const vvc355_col_mvf_frame *frame_dev, const vvc355_col_mvf_frame *frame_host);
+/* Host side (host/col_mvf.c, plain C, no HIP), on the downloaded entries.
+ * _unpack: mv sign-extended from 19 bits, ref_idx, pred_flag; a list that is not used gives mv 0 and ref_idx -1.
+ * _scatter: for every entry (gx, gy) of a width x height picture, writes mv, ref_idx and pred_flag of the MvField (vvc355_mvfield, 24 bytes)
+ * at (row 2 * gy, column 2 * gx) of the host table `tab_mvf` (fc->ref->tab_dmvr_mvf, min_pu_width entries per row) and NOTHING else: not
+ * the entry's other fields, not the entries at odd positions, which nobody reads as collocated motion. */
+void vvc355_col_mv_unpack(const vvc355_col_mv *e, int32_t mv[2][2], int8_t ref_idx[2], uint8_t *pred_flag);
+void vvc355_col_mvf_scatter(const vvc355_col_mv *col, int col_stride, int width, int height, void *tab_mvf, int min_pu_width);
+
 /* VVCLMCSDSPContext.filter — vvcdsp.h:124, vvc_filter_template.c:25 */
 void vvc355_lmcs_filter(int bd, uint8_t *dst, ptrdiff_t dst_stride, int width, int height, const uint8_t *lut);
 /* VVCSAODSPContext.band_filter[*] — vvcdsp.h:138, h2656_sao_template.c:24 */
