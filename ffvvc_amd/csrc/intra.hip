@@ -1329,47 +1329,162 @@ __global__ __launch_bounds__(256) void lmcs_vpdu_scale_kernel(const vvc355_lmcs_
         gst<int16_t>((int16_t *)f.scale + u, (int16_t)s);
 }
 
-// Sixteen lanes per chroma block, four blocks per wave (a typical block of an inter coding unit is 8x8: one step of four samples per lane;
-// a wave per block left three quarters of the lanes idle and the launch was bound by its wave count — one slot per transform block of the
-// picture, most of them empty).  The block's scale comes from the picture's table (joint bit 4); a job that wants it derived from the luma
-// plane (bit 3 alone) gets the whole wave for that, one such job after the other, before the groups add their blocks.
+// a value of lane `src` (any lane, per lane): ds_bpermute, every lane of the wave active
+__device__ __forceinline__ int lane_get(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
+
+// what the waves of a workgroup need of its 64 slots
+struct ResidSlots {
+    int incl[64];               // units of slots 0 .. i: unit u belongs to the first slot whose entry exceeds u
+    uint4 addr[64];             // dst, resid
+    uint4 par[64];              // dst_stride, scale, log2 w | joint << 8 | mode << 16, first unit
+    int total;
+};
+static constexpr int kResidWaves = 8, kResidUnroll = 4;
+
+// Sixty-four slots per workgroup of eight waves, and the slots' samples dealt evenly over all lanes.  The job array has one slot per
+// transform block of the picture, most of them empty and the full ones sorted by size (vvc355_itx_frame.resid_jobs).  Wave 0 reads
+// the slots, one per lane: first only the (w, h) dword, and where that holds a block the rest of the 56 bytes and the block's scale —
+// from the picture's table (joint bit 4), or derived from the luma plane (bit 3 alone) by the whole wave, one such job after the
+// other.  A block is w * h / 4 units of four consecutive samples of a row (w * h units of one sample for w < 4); a prefix sum over
+// the lanes numbers the workgroup's units and goes to LDS with each slot's addresses and parameters.  After the barrier a workgroup
+// of empty slots leaves; otherwise wave v takes units [256 (8 k + v), 256 (8 k + v + 1)), k = 0, 1, ..: four units per lane, the
+// unit's slot found by bisecting the prefix sums — sixty-four 8x8 blocks are one such step of four waves, sixty-four 32x32 blocks eight
+// steps of every wave, and a block's size no longer decides how many lanes work on it.  A unit is one int4 of residual and one
+// aligned 8-byte read-modify-write of the plane (4-byte at 8 bit): the column is a multiple of four; a block whose address or stride
+// is not aligned that far takes its four samples one by one.  The loads of a lane's four units go out before any is waited for.
 template <int BD>
-__global__ __launch_bounds__(256) void lmcs_chroma_resid_kernel(const vvc355_lmcs_resid_job *__restrict__ jobs, int n_jobs, const vvc355_lmcs_model *__restrict__ model)
+__global__ __launch_bounds__(64 * kResidWaves) void lmcs_chroma_resid_kernel(const vvc355_lmcs_resid_job *__restrict__ jobs, int n_jobs, const vvc355_lmcs_model *__restrict__ model)
 {
     using px_t = typename Px<BD>::type;
-    const int lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
-    const int first = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;             // the wave's four slots
-    if (first >= n_jobs)
-        return;
-    const int ji = first + g;
-    vvc355_lmcs_resid_job j = {};
-    if (ji < n_jobs) {
-        // 56 bytes: three 16-byte pieces and one of 8 (the struct is 8-byte aligned; the lanes of a group read the same addresses)
-        const uint2 *p = (const uint2 *)(jobs + ji);
-        uint2 q[7];
+    static_assert(offsetof(vvc355_lmcs_resid_job, h) == offsetof(vvc355_lmcs_resid_job, w) + 2 && offsetof(vvc355_lmcs_resid_job, w) % 4 == 0, "(w, h) is one dword");
+    constexpr int VB = 4 * (int)sizeof(px_t);                                  // bytes of a unit in the plane
+    __shared__ __attribute__((aligned(16))) ResidSlots S;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave == 0) {
+        const int ji = blockIdx.x * 64 + lane;                                // the lane's slot
+        const uint32_t wh = ji < n_jobs ? gld<uint32_t>((const uint8_t *)(jobs + ji) + offsetof(vvc355_lmcs_resid_job, w)) : 0u;
+        const bool full = (int16_t)wh > 0 && (int16_t)(wh >> 16) > 0;
+        if (!__builtin_amdgcn_ballot_w64(full)) {
+            if (lane == 0)
+                S.total = 0;                                                    // only empty slots, or past the end
+        } else {
+            vvc355_lmcs_resid_job j = {};
+            if (full) {
+                const uint2 *p = (const uint2 *)(jobs + ji);                    // 56 bytes, 8-byte aligned
+                uint2 q[7];
 #pragma unroll
-        for (int i = 0; i < 7; i++) q[i] = gld<uint2>(p + i);
-        __builtin_memcpy(&j, q, sizeof(j));
+                for (int i = 0; i < 7; i++) q[i] = gld<uint2>(p + i);
+                __builtin_memcpy(&j, q, sizeof(j));
+            }
+            int scale = 0;
+            unsigned long long todo = __builtin_amdgcn_ballot_w64(full && (j.joint & 8) && !(j.joint & 16));
+            while (todo) {                           // wave-uniform: the slot's parameters from its lane
+                const int src = __builtin_ctzll(todo);
+                todo &= todo - 1;
+                auto u32 = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); };
+                const uint64_t luma = (uint64_t)u32((uint32_t)j.luma) | ((uint64_t)u32((uint32_t)(j.luma >> 32)) << 32);
+                const int s_ = lmcs_scale_from_plane<BD>(model, (const uint8_t *)luma, (int)u32((uint32_t)j.luma_stride) / (int)sizeof(px_t), (int16_t)u32((uint16_t)j.x_vpdu),
+                                                         (int16_t)u32((uint16_t)j.y_vpdu), (int16_t)u32((uint16_t)j.size_y), u32(j.avail_l) != 0, u32(j.avail_t) != 0,
+                                                         (int16_t)u32((uint16_t)j.pic_w), (int16_t)u32((uint16_t)j.pic_h), lane);
+                if (lane == src)
+                    scale = s_;
+            }
+            if (full && (j.joint & 16))
+                scale = (int)gld<int16_t>((const int16_t *)j.luma);
+            // mode 0: units of four samples, one vector access; 1: the same units, sample by sample; 2: units of one sample (w < 4)
+            const int mode = j.w < 4 ? 2 : ((j.dst | (uint64_t)(uint32_t)j.dst_stride) & (VB - 1)) ? 1 : 0;
+            const int units = full ? (mode == 2 ? j.w * j.h : (j.w * j.h) >> 2) : 0;
+            int incl = units;                        // inclusive prefix sum over the lanes
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int t = lane_get(incl, lane - d);
+                if (lane >= d)
+                    incl += t;
+            }
+            S.incl[lane] = incl;
+            S.addr[lane] = make_uint4((uint32_t)j.dst, (uint32_t)(j.dst >> 32), (uint32_t)j.resid, (uint32_t)(j.resid >> 32));
+            S.par[lane] = make_uint4((uint32_t)j.dst_stride, (uint32_t)scale, (uint32_t)(ilog2i(full ? j.w : 1) | (int)j.joint << 8 | mode << 16), (uint32_t)(incl - units));
+            if (lane == 63)
+                S.total = incl;
+        }
     }
-    int scale = 0;
-    const bool derive = j.w > 0 && (j.joint & 8) && !(j.joint & 16);
-    unsigned long long todo = __builtin_amdgcn_ballot_w64(derive && l16 == 0);
-    while (todo) {                                   // wave-uniform: the group's parameters through its first lane
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        auto u32 = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); };
-        const uint64_t luma = (uint64_t)u32((uint32_t)j.luma) | ((uint64_t)u32((uint32_t)(j.luma >> 32)) << 32);
-        const int s_ = lmcs_scale_from_plane<BD>(model, (const uint8_t *)luma, (int)u32((uint32_t)j.luma_stride) / (int)sizeof(px_t), (int16_t)u32((uint16_t)j.x_vpdu),
-                                                 (int16_t)u32((uint16_t)j.y_vpdu), (int16_t)u32((uint16_t)j.size_y), u32(j.avail_l) != 0, u32(j.avail_t) != 0,
-                                                 (int16_t)u32((uint16_t)j.pic_w), (int16_t)u32((uint16_t)j.pic_h), lane);
-        if (g == (src >> 4))
-            scale = s_;
+    __syncthreads();
+    const int total = S.total;
+
+    for (int base = wave * (64 * kResidUnroll); base < total; base += kResidWaves * 64 * kResidUnroll) {
+        bool fast[kResidUnroll], slow[kResidUnroll];
+        uint8_t *p[kResidUnroll];
+        const int *res[kResidUnroll];
+        int sc[kResidUnroll], mt[kResidUnroll], xo[kResidUnroll];
+#pragma unroll
+        for (int u = 0; u < kResidUnroll; u++) {
+            const int i = base + u * 64 + lane, ic = min(i, total - 1);
+            int s = 0;                               // the slot of unit ic: the number of slots whose units all come before it
+#pragma unroll
+            for (int step = 32; step; step >>= 1)
+                if (S.incl[s + step - 1] <= ic)
+                    s += step;
+            const uint4 ad = S.addr[s], pr = S.par[s];
+            mt[u] = (int)pr.z;
+            sc[u] = (int)pr.y;
+            const int lw = mt[u] & 0xff, md = mt[u] >> 16, t = ic - (int)pr.w, e = md == 2 ? t : t * 4;
+            xo[u] = e & ((1 << lw) - 1);
+            p[u] = (uint8_t *)((uint64_t)ad.x | (uint64_t)ad.y << 32) + row_off(e >> lw, (int)pr.x);       // the unit's row
+            res[u] = (const int *)((uint64_t)ad.z | (uint64_t)ad.w << 32) + e;
+            fast[u] = i < total && md == 0;
+            slow[u] = i < total && md != 0;
+            if (md == 0)
+                p[u] += xo[u] * (int)sizeof(px_t);
+        }
+        int4 r4[kResidUnroll];
+        uint2 d[kResidUnroll];
+#pragma unroll
+        for (int u = 0; u < kResidUnroll; u++) {
+            r4[u] = make_int4(0, 0, 0, 0);
+            d[u] = make_uint2(0, 0);
+            if (fast[u]) {
+                r4[u] = gld<int4>(res[u]);
+                if constexpr (BD > 8)
+                    d[u] = gld<uint2>(p[u]);
+                else
+                    d[u].x = gld<uint32_t>(p[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kResidUnroll; u++) {
+            // resid_sample (resid_math.hpp) without branches — joint differs from lane to lane here: sign and shift are 1 and 0 without
+            // bit 0, and lmcs_scale_chroma's two arms are one product of the magnitude with the sign put back
+            const int joint = (mt[u] >> 8) & 0xff, scl = sc[u];
+            const int sgn = (joint & 3) == 3 ? -1 : 1, sh = (joint & 5) == 5 ? 1 : 0;
+            auto sample = [&](int r) {
+                r = (r * sgn) >> sh;
+                const int c = clip_intp2(r, BD), m = (abs(c) * scl + (1 << 10)) >> 11;
+                return (joint & 8) ? (c < 0 ? -m : m) : r;
+            };
+            if (fast[u]) {
+                if constexpr (BD > 8) {
+                    uint2 o;
+                    o.x = (uint32_t)clip_px<BD>((int)(d[u].x & 0xffff) + sample(r4[u].x)) | (uint32_t)clip_px<BD>((int)(d[u].x >> 16) + sample(r4[u].y)) << 16;
+                    o.y = (uint32_t)clip_px<BD>((int)(d[u].y & 0xffff) + sample(r4[u].z)) | (uint32_t)clip_px<BD>((int)(d[u].y >> 16) + sample(r4[u].w)) << 16;
+                    gst<uint2>(p[u], o);
+                } else {
+                    const uint32_t v = d[u].x;
+                    gst<uint32_t>(p[u], (uint32_t)clip_px<BD>((int)(v & 0xff) + sample(r4[u].x)) | (uint32_t)clip_px<BD>((int)((v >> 8) & 0xff) + sample(r4[u].y)) << 8 |
+                                        (uint32_t)clip_px<BD>((int)((v >> 16) & 0xff) + sample(r4[u].z)) << 16 | (uint32_t)clip_px<BD>((int)(v >> 24) + sample(r4[u].w)) << 24);
+                }
+            } else if (slow[u]) {
+                if ((mt[u] >> 16) == 1) {
+                    const int4 q4 = gld<int4>(res[u]);
+                    const int r[4] = { q4.x, q4.y, q4.z, q4.w };
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+                        st_px<BD>(p[u], xo[u] + q, clip_px<BD>(ld_px<BD>(p[u], xo[u] + q) + sample(r[q])));
+                } else {
+                    st_px<BD>(p[u], xo[u], clip_px<BD>(ld_px<BD>(p[u], xo[u]) + sample(gld<int>(res[u]))));
+                }
+            }
+        }
     }
-    if (j.w <= 0)
-        return;                 // an empty slot of a job array the transform-block builder wrote (vvc355_itx_frame.resid_jobs), or past the end
-    if (j.joint & 16)
-        scale = (int)gld<int16_t>((const int16_t *)j.luma);
-    resid_block_add<BD, 16>((uint8_t *)j.dst, j.dst_stride, (const int *)j.resid, j.w, j.h, j.joint, scale, l16);
 }
 
 } // namespace vvc355
@@ -1392,7 +1507,7 @@ void vvc355_lmcs_vpdu_scale_pass(void *stream, int bd, const vvc355_lmcs_scale_f
 void vvc355_lmcs_chroma_resid_batch(void *stream, int bd, const vvc355_lmcs_resid_job *jobs_dev, int n_jobs, const vvc355_lmcs_model *model_dev)
 {
     if (n_jobs <= 0) return;
-    VVC355_BD_DISPATCH(bd, hipLaunchKernelGGL((vvc355::lmcs_chroma_resid_kernel<BD>), dim3((n_jobs + 15) / 16), dim3(256), 0, (hipStream_t)stream, jobs_dev, n_jobs, model_dev));
+    VVC355_BD_DISPATCH(bd, hipLaunchKernelGGL((vvc355::lmcs_chroma_resid_kernel<BD>), dim3((n_jobs + 63) / 64), dim3(64 * vvc355::kResidWaves), 0, (hipStream_t)stream, jobs_dev, n_jobs, model_dev));
     HIP_CHECK(hipGetLastError());
 }
 
