@@ -177,6 +177,10 @@ BATCH_SIGNATURES = {
     "deblock_bs_rec_pass": ("i", "ppp"),
     # the QP tables of deblock_frame_pass from the same records and two sidecars of one / two bytes per record (vvc355_qp_rec_frame)
     "deblock_qp_rec_pass": ("i", "ppp"),
+    # the MvField table from one 64-byte record per prediction unit (vvc355_mvf_unit_frame): plain, affine (from control points, with the
+    # PROF switches and offsets of the affine stage's records) and GPM units; the second entry is the record check, host only
+    "mvf_unit_pass":    ("i", "ppp"),
+    "mvf_unit_check":   ("i", "ppi"),
     # inverse luma mapping of a whole picture from the per-CTB slice index and the per-slice flags (vvc355_lmcs_frame): no job array
     "lmcs_frame_pass":  ("i", "pipp"),
     # a decoded picture's checksums where it lies (vvc355_pic_digest_frame): framecrc's Adler-32, the SEI's checksum and CRC per component
@@ -749,6 +753,34 @@ class QpRecFrame(ctypes.Structure):
 # what vvc355_deblock_qp_rec_pass returns for a frame it refuses (VVC355_QP_REC_E_*)
 (QP_REC_E_FRAME, QP_REC_E_SIZE, QP_REC_E_CTB, QP_REC_E_GRID, QP_REC_E_PITCH, QP_REC_E_COMP, QP_REC_E_COUNT, QP_REC_E_RECORDS,
  QP_REC_E_SIDECAR, QP_REC_E_OUTPUT) = -1, -2, -3, -4, -5, -6, -7, -8, -9, -10
+
+
+MVF_PLAIN, MVF_AFFINE, MVF_GPM = 0, 1, 2          # VVC355_MVF_*: vvc355_mvf_unit.kind
+MVF_LINK_NONE = 0xFFFFFFFF                        # VVC355_MVF_LINK_NONE
+
+
+class MvfUnit(ctypes.Structure):
+    """Mirror of vvc355_mvf_unit (body: a MvField | cp_mv[2][3][2] | two MvField)."""
+    _fields_ = [("x0", ctypes.c_int16), ("y0", ctypes.c_int16), ("w", ctypes.c_uint8), ("h", ctypes.c_uint8), ("kind", ctypes.c_uint8),
+                ("aux", ctypes.c_uint8), ("link", ctypes.c_uint32), ("pf", ctypes.c_uint8), ("ref_idx", ctypes.c_int8 * 2),
+                ("pad_", ctypes.c_uint8), ("body", ctypes.c_int32 * 12)]
+
+
+class MvfUnitFrame(ctypes.Structure):
+    """Mirror of vvc355_mvf_unit_frame."""
+    _fields_ = [("units", ctypes.c_uint64), ("ctu_first", ctypes.c_uint64), ("mvf", ctypes.c_uint64), ("affine_cus", ctypes.c_uint64),
+                ("n_units", ctypes.c_int32), ("n_affine_cus", ctypes.c_int32), ("mvf_pitch", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ctb_width", ctypes.c_int32), ("ctb_height", ctypes.c_int32),
+                ("ctb_log2", ctypes.c_uint8), ("prof_disabled", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 2)]
+
+
+# what vvc355_mvf_unit_pass returns for a frame it refuses (VVC355_MVF_UNIT_E_*)
+(MVF_UNIT_E_FRAME, MVF_UNIT_E_SIZE, MVF_UNIT_E_COUNT, MVF_UNIT_E_CTB, MVF_UNIT_E_GRID, MVF_UNIT_E_PITCH, MVF_UNIT_E_RECORDS,
+ MVF_UNIT_E_AFFINE) = -1, -2, -3, -4, -5, -6, -7, -8
+# which rule a record breaks (vvc355_mvf_unit_check, VVC355_MVF_UNIT_R_*)
+(MVF_UNIT_R_SIDE, MVF_UNIT_R_PLACE, MVF_UNIT_R_CTU, MVF_UNIT_R_PAD, MVF_UNIT_R_KIND, MVF_UNIT_R_AFF_SHAPE, MVF_UNIT_R_AFF_MODEL,
+ MVF_UNIT_R_AFF_PRED, MVF_UNIT_R_AFF_LINK, MVF_UNIT_R_GPM_SHAPE, MVF_UNIT_R_GPM_RATIO, MVF_UNIT_R_GPM_PART,
+ MVF_UNIT_R_GPM_PRED) = range(1, 14)
 
 
 class LmcsFrame(ctypes.Structure):

@@ -1448,6 +1448,95 @@ enum { VVC355_QP_REC_E_FRAME = -1, VVC355_QP_REC_E_SIZE = -2, VVC355_QP_REC_E_CT
  * returns 0, or a negative VVC355_QP_REC_E_* with NOTHING launched */
 int vvc355_deblock_qp_rec_pass(void *stream, const vvc355_qp_rec_frame *frame_dev, const vvc355_qp_rec_frame *frame_host);
 
+/* ------------------------------------------------------------------ MvField table from prediction-unit records (mvf_unit.hip) */
+
+/*
+ * The MvField table written from ONE fixed-size record per prediction unit, the reference's three storage rules run on the device.
+ * vvc355_tab_fill_pass takes one vvc355_mv_rec per rectangle of equal motion, which for a regular unit is one call of ff_vvc_store_mvf /
+ * ff_vvc_store_mv; for the two kinds whose field is computed per 4x4 block — ff_vvc_store_sb_mvs (vvc_mvs.c:402-446) from control
+ * points, ff_vvc_store_gpm_mvf (:448-491) from two candidates and a partition — the host would have to run the derivation and upload up
+ * to one 32-byte record per 4x4 block (8 KiB for a 64x64 affine unit whose inputs are 48 bytes).  Here such a unit is one 64-byte record:
+ *   VVC355_MVF_PLAIN   every entry of the rectangle gets body[0..5] (a vvc355_mvfield) verbatim, pad bytes included: ff_vvc_store_mvf,
+ *                      ff_vvc_store_mv, one sub-block of a sub-block temporal merge unit, an intra unit (a zero MvField: PF_INTRA).
+ *   VVC355_MVF_AFFINE  body = cp_mv[list][control point][x, y] (mi->mv[list][cp]), aux = motion_model_idc (1: 4 parameters, 2: 6),
+ *                      pf = pred_flag | hpel_if_idx << 2 | bcw_idx << 4.  Per list in pred_flag: SubblockParams of init_subblock_params
+ *                      (:338-359), the fallback decision of is_fallback_mode (:313-336, per list), then per 4x4 sub-block (sbx, sby) the
+ *                      position 2 + 4 * sb (cb >> 1 under fallback), mv = mv_scale + d_hor * x_pos + d_ver * y_pos, ff_vvc_round_mv(., 0, 7)
+ *                      and the clip to [-2^17, 2^17 - 1].  The entry has pred_flag, hpel_if_idx, bcw_idx and BOTH ref_idx from the
+ *                      record, ciip_flag 0 and pad 0; the motion of a list not in pred_flag is 0 (the reference leaves what its stack
+ *                      held there, and in that list's ref_idx).  Where link != VVC355_MVF_LINK_NONE the pass also writes, into
+ *                      affine_cus[link], prof_flags (bit l = cb_prof_flag[l] of derive_cb_prof_flag_lx :282-298: 0 with prof_disabled,
+ *                      under fallback, with equal control points, or for a list not in pred_flag; the other six bits 0) and all 64
+ *                      diff_mv of derive_subblock_diff_mvs (:361-379: rounded with shift 8, clipped to +-31; zeros where the flag is 0).
+ *                      No other byte of that vvc355_affine_cu is written.  Two records must not link the same vvc355_affine_cu.
+ *   VVC355_MVF_GPM     body = pu->gpm_mv[0..1] (two vvc355_mvfield), aux = gpm_partition_idx.  Per 4x4 block motion_idx and s_type
+ *                      (:469-471); the entry is gpm_mv[0] verbatim, gpm_mv[1] verbatim (s_type 1, or s_type 2 with both parts in one
+ *                      list), or the combination: gpm_mv[0] with pred_flag = PF_BI and mv / ref_idx of list gpm_mv[1].pred_flag - 1 from
+ *                      gpm_mv[1].
+ * All results are byte-exact.  Placement: the rectangles of one picture's records do not overlap; every covered entry (x >> 2, y >> 2)
+ * is written whole (24 bytes); entries no record covers keep their bytes.  Records are grouped per CTU in raster order as for
+ * vvc355_tab_fill: ctu_first[rs] .. ctu_first[rs + 1] is CTU rs's range (clamped to n_units and to 65535 records; a ctu_first that
+ * decreases makes that CTU's range empty).
+ *
+ * Records are NOT trusted.  A malformed record is skipped — no entry and no vvc355_affine_cu is written for it, and of the record only
+ * the fields the check needs are read.  vvc355_mvf_unit_check is that check (the same predicate the kernel runs), in this order:
+ *   _R_SIDE      w or h zero, no multiple of 4, or above 128
+ *   _R_PLACE     x0 or y0 negative or no multiple of 4, or the rectangle not inside the picture
+ *   _R_CTU       the rectangle not inside the CTU it is filed under
+ *   _R_PAD       pad_ != 0                      _R_KIND       kind above VVC355_MVF_GPM
+ *   _R_AFF_SHAPE a side below 8 or no power of two             _R_AFF_MODEL  aux not 1 or 2
+ *   _R_AFF_PRED  pf & 3 == 0                    _R_AFF_LINK   link neither VVC355_MVF_LINK_NONE nor below n_affine_cus
+ *   _R_GPM_SHAPE a side outside 8..64           _R_GPM_RATIO  one side 8 or more times the other
+ *   _R_GPM_PART  aux above 63                   _R_GPM_PRED   a part whose pred_flag is not 1 or 2
+ * Domain: control points lie within the 18-bit motion range [-2^17, 2^17 - 1]; beyond it the reference's int arithmetic may overflow,
+ * which is undefined there (this pass wraps).  No implicit padding: the record is 64 bytes (16-byte aligned in the array), the frame 64.
+ */
+enum { VVC355_MVF_PLAIN = 0, VVC355_MVF_AFFINE = 1, VVC355_MVF_GPM = 2 };
+#define VVC355_MVF_LINK_NONE 0xFFFFFFFFu
+typedef struct vvc355_mvf_unit {
+    int16_t  x0, y0;              /* luma samples, multiples of 4 */
+    uint8_t  w, h;                /* multiples of 4, up to 128 */
+    uint8_t  kind;                /* VVC355_MVF_* */
+    uint8_t  aux;                 /* AFFINE: motion_model_idc; GPM: gpm_partition_idx; PLAIN: not read */
+    uint32_t link;                /* AFFINE: index into frame.affine_cus, or VVC355_MVF_LINK_NONE; other kinds: not read */
+    uint8_t  pf;                  /* AFFINE: pred_flag | hpel_if_idx << 2 | bcw_idx << 4 */
+    int8_t   ref_idx[2];          /* AFFINE */
+    uint8_t  pad_;                /* 0 */
+    int32_t  body[12];            /* see above; what a kind does not use is not read */
+} vvc355_mvf_unit;
+typedef struct vvc355_mvf_unit_frame {
+    uint64_t units;               /* DEVICE vvc355_mvf_unit[n_units], 16-byte aligned */
+    uint64_t ctu_first;           /* DEVICE int32[ctb_width * ctb_height + 1] */
+    uint64_t mvf;                 /* DEVICE vvc355_mvfield per 4x4 luma unit, row pitch mvf_pitch, 8-byte aligned: the OUTPUT */
+    uint64_t affine_cus;          /* DEVICE vvc355_affine_cu[n_affine_cus], 16-byte aligned, or 0: prof_flags and diff_mv are OUTPUTS */
+    int32_t  n_units, n_affine_cus;
+    int32_t  mvf_pitch;
+    int32_t  width, height, ctb_width, ctb_height;     /* luma picture size; CTUs per row / column */
+    uint8_t  ctb_log2;
+    uint8_t  prof_disabled;       /* ph_prof_disabled_flag */
+    uint8_t  pad_[2];
+} vvc355_mvf_unit_frame;
+
+/* what vvc355_mvf_unit_pass returns for a frame it refuses, in the order checked: no frame (either copy); width or height <= 0, no
+ * multiple of 4 or above 32764; a negative count; ctb_log2 outside 5..7; ctb_width / ctb_height not ceil(size >> ctb_log2); mvf_pitch <
+ * ceil(width / 4); with n_units > 0, units, ctu_first or mvf missing or misaligned (16 / 4 / 8 bytes); with n_affine_cus > 0, affine_cus
+ * missing or not 16-byte aligned */
+enum { VVC355_MVF_UNIT_E_FRAME = -1, VVC355_MVF_UNIT_E_SIZE = -2, VVC355_MVF_UNIT_E_COUNT = -3, VVC355_MVF_UNIT_E_CTB = -4,
+       VVC355_MVF_UNIT_E_GRID = -5, VVC355_MVF_UNIT_E_PITCH = -6, VVC355_MVF_UNIT_E_RECORDS = -7, VVC355_MVF_UNIT_E_AFFINE = -8 };
+/* which rule a record breaks (vvc355_mvf_unit_check; see above) */
+enum { VVC355_MVF_UNIT_R_SIDE = 1, VVC355_MVF_UNIT_R_PLACE = 2, VVC355_MVF_UNIT_R_CTU = 3, VVC355_MVF_UNIT_R_PAD = 4,
+       VVC355_MVF_UNIT_R_KIND = 5, VVC355_MVF_UNIT_R_AFF_SHAPE = 6, VVC355_MVF_UNIT_R_AFF_MODEL = 7, VVC355_MVF_UNIT_R_AFF_PRED = 8,
+       VVC355_MVF_UNIT_R_AFF_LINK = 9, VVC355_MVF_UNIT_R_GPM_SHAPE = 10, VVC355_MVF_UNIT_R_GPM_RATIO = 11,
+       VVC355_MVF_UNIT_R_GPM_PART = 12, VVC355_MVF_UNIT_R_GPM_PRED = 13 };
+/* One launch on `stream`, one workgroup per CTU, no device scratch, no atomics, no host synchronisation: it can be captured in a graph.
+ * The host copy of the frame is checked before any HIP call.  n_units == 0 launches nothing and returns 0.
+ * returns 0, or a negative VVC355_MVF_UNIT_E_* with NOTHING launched */
+int vvc355_mvf_unit_pass(void *stream, const vvc355_mvf_unit_frame *frame_dev, const vvc355_mvf_unit_frame *frame_host);
+/* HOST only, no HIP call: 0 for a record the pass would place when filed under CTU ctu_rs of `frame` (of which width, height, ctb_log2,
+ * ctb_width, ctb_height and n_affine_cus are read), or the VVC355_MVF_UNIT_R_* of the first rule it breaks; -1 without a record or a
+ * frame, with ctb_log2 outside 5..7 or ctu_rs outside the CTU grid */
+int vvc355_mvf_unit_check(const vvc355_mvf_unit *rec, const vvc355_mvf_unit_frame *frame, int ctu_rs);
+
 /* ------------------------------------------------------------------ SAO stage driver (loopfilter.hip) */
 
 /*
