@@ -102,6 +102,29 @@ template <int BD> __device__ __forceinline__ int lmcs_fwd(const uint8_t *lut, in
 template <typename T> __device__ __forceinline__ T gld_at(const uint8_t *base, uint32_t off) { return gld<T>(base + (size_t)off); }
 template <typename T> __device__ __forceinline__ void gst_at(uint8_t *base, uint32_t off, T v) { gst<T>(base + (size_t)off, v); }
 
+// Descriptor builders (inter_build_kernel, itx_build_kernel): a lane that stores its own 48..104-byte record field by field touches a
+// line per store instruction and lane.  The lane writes the record as one row of N dwords in LDS instead — the pitch is odd, so 32 lanes
+// writing dword k of their rows hit 32 banks — and after a barrier the workgroup copies the rows out as one contiguous range, consecutive
+// lanes storing consecutive 8-byte pairs: whole lines per wave instruction.
+template <int PITCH, typename T> __device__ __forceinline__ void lds_row_put(uint32_t *rows, int r, const T &v)
+{
+    static_assert(sizeof(T) % 8 == 0 && PITCH % 2 == 1 && PITCH * 4 > (int)sizeof(T), "whole 8-byte pairs, odd pitch");
+    uint32_t w[sizeof(T) / 4];
+    __builtin_memcpy(w, &v, sizeof(T));
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(T) / 4); k++) rows[r * PITCH + k] = w[k];
+}
+// Rows [0, n_rows) of N dwords each go to dst, dst + 4 N, ...: exactly n_rows * N dwords, nothing beyond.  dst is 8-byte aligned (the
+// records hold 64-bit fields).  Every lane of the workgroup calls it, after the barrier that follows the last lds_row_put.
+template <int N, int PITCH> __device__ __forceinline__ void lds_rows_to_global(const uint32_t *rows, void *dst, int n_rows)
+{
+    static_assert(N % 2 == 0 && PITCH % 2 == 1 && PITCH > N, "whole 8-byte pairs, odd pitch");
+    for (int p = threadIdx.x; p < n_rows * (N / 2); p += blockDim.x) {
+        const int r = p / (N / 2), k = 2 * (p - r * (N / 2));
+        gst<uint2>((uint8_t *)dst + (size_t)p * 8, make_uint2(rows[r * PITCH + k], rows[r * PITCH + k + 1]));
+    }
+}
+
 // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  xcd_chunked() renumbers workgroup b of n so that every
 // XCD works through one contiguous eighth of the job list: neighbouring jobs — neighbouring blocks of the picture, whose
 // reference windows overlap — then meet in the same L2 instead of being fetched from HBM once per XCD.

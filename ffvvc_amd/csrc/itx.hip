@@ -821,49 +821,61 @@ static void launch_itx_shape_any(hipStream_t st, const vvc355_itx_job *jobs_dev,
     }
 }
 
-// one lane per transform block record: the 48-byte job the transform kernels consume (vvc355_itx_frame_build)
+// one lane per transform block record: the 48-byte job the transform kernels consume (vvc355_itx_frame_build), and the chroma residual job
+// where the frame asks for them.  The lane leaves both as rows in LDS; the workgroup's 256 jobs, contiguous in either array, go out through
+// lds_rows_to_global.
 __global__ __launch_bounds__(256) void itx_build_kernel(const vvc355_itx_frame *__restrict__ fp)
 {
+    constexpr int WG = 256, JOB_DW = sizeof(vvc355_itx_job) / 4, RES_DW = sizeof(vvc355_lmcs_resid_job) / 4;
+    __shared__ uint32_t s_jobs[WG * (JOB_DW + 1)], s_resid[WG * (RES_DW + 1)];
     const vvc355_itx_frame f = load_uniform(fp);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= f.n_tus)
-        return;
-    const vvc355_itx_tu t = ((const vvc355_itx_tu *)f.tus)[i];
-    vvc355_itx_job j = {};
-    j.coeffs = f.coeffs + (uint64_t)t.coeff_off * 4;
-    const int c = t.c_idx;
-    const uint64_t plane = c == 0 ? f.plane[0] : c == 1 ? f.plane[1] : f.plane[2];
-    const int stride = c == 0 ? f.stride[0] : c == 1 ? f.stride[1] : f.stride[2];
-    const bool keep = (t.flags & 4) != 0;
-    j.dst = keep ? 0 : plane + (uint64_t)t.y0 * stride + ((uint64_t)t.x0 << f.pixel_shift);
-    j.dst_stride = stride;
-    j.trh = t.tr & 15; j.trv = t.tr >> 4;
-    j.log2_w = t.log2_w; j.log2_h = t.log2_h; j.nzw = t.nzw; j.nzh = t.nzh;
-    j.range = f.range; j.bd = f.bd;
-    j.store_coeffs = keep;
-    j.dq_flags = (uint8_t)((t.flags & 1) | (t.flags & 2)); j.dq_qp = t.qp;
-    j.log2_matrix_size = 1; j.dc = -1;
-    j.mts_flags = (t.flags & 8) ? VVC355_ITX_DERIVE_TYPE : 0; j.tu_flags = f.tu_flags; j.c_idx = t.c_idx;
-    ((vvc355_itx_job *)f.jobs)[i] = j;
-    if (f.resid_jobs) {
-        vvc355_lmcs_resid_job r = {};
-        if (t.flags & 64) {
-            r.dst = plane + (uint64_t)t.y0 * stride + ((uint64_t)t.x0 << f.pixel_shift);
-            r.resid = j.coeffs; r.luma = f.plane[0];
-            r.dst_stride = stride; r.luma_stride = f.stride[0];
-            r.w = (int16_t)(1 << t.log2_w); r.h = (int16_t)(1 << t.log2_h);
-            r.x_vpdu = (int16_t)((t.x0 << (c ? f.hs : 0)) & ~(f.size_y - 1)); r.y_vpdu = (int16_t)((t.y0 << (c ? f.vs : 0)) & ~(f.size_y - 1));
-            r.pic_w = (int16_t)f.width; r.pic_h = (int16_t)f.height; r.size_y = f.size_y;
-            r.avail_l = (t.flags >> 4) & 1; r.avail_t = (t.flags >> 5) & 1;
-            r.joint = 8;
-            if (f.scale_table) {          // the unit's entry of vvc355_lmcs_vpdu_scale_pass's table instead of a derivation per block
-                const int ux = (f.width + f.size_y - 1) / f.size_y;
-                r.luma = f.scale_table + (uint64_t)((r.y_vpdu / f.size_y) * ux + r.x_vpdu / f.size_y) * 2;
-                r.joint = 8 | 16;
+    const int tid = threadIdx.x, first = blockIdx.x * WG, n = min(WG, f.n_tus - first);
+    if (tid < n) {
+        uint32_t tw[sizeof(vvc355_itx_tu) / 4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) tw[k] = gld<uint32_t>((const uint32_t *)f.tus + (size_t)(first + tid) * 4 + k);
+        vvc355_itx_tu t;
+        __builtin_memcpy(&t, tw, sizeof(t));
+        vvc355_itx_job j = {};
+        j.coeffs = f.coeffs + (uint64_t)t.coeff_off * 4;
+        const int c = t.c_idx;
+        const uint64_t plane = c == 0 ? f.plane[0] : c == 1 ? f.plane[1] : f.plane[2];
+        const int stride = c == 0 ? f.stride[0] : c == 1 ? f.stride[1] : f.stride[2];
+        const bool keep = (t.flags & 4) != 0;
+        j.dst = keep ? 0 : plane + (uint64_t)t.y0 * stride + ((uint64_t)t.x0 << f.pixel_shift);
+        j.dst_stride = stride;
+        j.trh = t.tr & 15; j.trv = t.tr >> 4;
+        j.log2_w = t.log2_w; j.log2_h = t.log2_h; j.nzw = t.nzw; j.nzh = t.nzh;
+        j.range = f.range; j.bd = f.bd;
+        j.store_coeffs = keep;
+        j.dq_flags = (uint8_t)((t.flags & 1) | (t.flags & 2)); j.dq_qp = t.qp;
+        j.log2_matrix_size = 1; j.dc = -1;
+        j.mts_flags = (t.flags & 8) ? VVC355_ITX_DERIVE_TYPE : 0; j.tu_flags = f.tu_flags; j.c_idx = t.c_idx;
+        lds_row_put<JOB_DW + 1>(s_jobs, tid, j);
+        if (f.resid_jobs) {
+            vvc355_lmcs_resid_job r = {};
+            if (t.flags & 64) {
+                r.dst = plane + (uint64_t)t.y0 * stride + ((uint64_t)t.x0 << f.pixel_shift);
+                r.resid = j.coeffs; r.luma = f.plane[0];
+                r.dst_stride = stride; r.luma_stride = f.stride[0];
+                r.w = (int16_t)(1 << t.log2_w); r.h = (int16_t)(1 << t.log2_h);
+                r.x_vpdu = (int16_t)((t.x0 << (c ? f.hs : 0)) & ~(f.size_y - 1)); r.y_vpdu = (int16_t)((t.y0 << (c ? f.vs : 0)) & ~(f.size_y - 1));
+                r.pic_w = (int16_t)f.width; r.pic_h = (int16_t)f.height; r.size_y = f.size_y;
+                r.avail_l = (t.flags >> 4) & 1; r.avail_t = (t.flags >> 5) & 1;
+                r.joint = 8;
+                if (f.scale_table) {          // the unit's entry of vvc355_lmcs_vpdu_scale_pass's table instead of a derivation per block
+                    const int ux = (f.width + f.size_y - 1) / f.size_y;
+                    r.luma = f.scale_table + (uint64_t)((r.y_vpdu / f.size_y) * ux + r.x_vpdu / f.size_y) * 2;
+                    r.joint = 8 | 16;
+                }
             }
+            lds_row_put<RES_DW + 1>(s_resid, tid, r);
         }
-        ((vvc355_lmcs_resid_job *)f.resid_jobs)[i] = r;
     }
+    __syncthreads();
+    lds_rows_to_global<JOB_DW, JOB_DW + 1>(s_jobs, (vvc355_itx_job *)f.jobs + first, n);
+    if (f.resid_jobs)
+        lds_rows_to_global<RES_DW, RES_DW + 1>(s_resid, (vvc355_lmcs_resid_job *)f.resid_jobs + first, n);
 }
 
 // ------------------------------------------------------------------------------------------------ intra transform stage from records
