@@ -16,11 +16,13 @@
  * digests in tests/golden/ref_slots.json and, where the reference is present, a wider sweep
  * (tests/test_oracle_ref_cpu.py).  Pinned on whole pictures against the reference's own callers
  * (ref_shim_filter.c, tests/ref_pass_cases.py, tests/golden/ref_passes.json): orc_deblock_bs_pass,
- * orc_deblock_frame_pass, orc_sao_frame_pass, orc_alf_frame_pass.
+ * orc_deblock_frame_pass, orc_sao_frame_pass, orc_alf_frame_pass; (ref_shim_inter.c,
+ * tests/ref_inter_cases.py, tests/golden/ref_inter.json): orc_bipred_block, orc_gpm_block,
+ * orc_affine_block, orc_inter_frame_build / _pass; (ref_recon_picture of ref_shim_intra.c,
+ * tests/ref_recon_cases.py, tests/golden/ref_recon.json): orc_recon_frame_pass,
+ * orc_lmcs_chroma_resid_block, orc_lmcs_vpdu_scale_pass.
  * STILL UNPINNED, cross-checked only by independent properties (tests/test_oracle_cpu.py):
- * the other caller restatements (orc_bipred_block, orc_gpm_block, orc_affine_block,
- * orc_lmcs_chroma_resid_block, orc_inter_frame_build / _pass, orc_recon_frame_pass,
- * orc_tab_fill_pass, orc_lmcs_vpdu_scale_pass).
+ * orc_tab_fill_pass.
  *
  * Conventions: `bd` = bit depth (8, 10 or 12); pixels are uint8_t when bd == 8 and uint16_t
  * otherwise; pixel strides are in BYTES exactly as on the reference's function-pointer surface

@@ -1,7 +1,8 @@
 /*
  * oracle/orc_recon.c — the RECON stage of a picture as the decoder runs it per CTU, and the two transform-side helpers that sit
- * between dequant and the inverse transform (TEST INFRASTRUCTURE ONLY; the two helpers PINNED, the RECON walk UNPINNED apart from its
- * availability derivation, which tests/test_oracle_ref_cpu.py compares with the reference's; see orc_common.h).
+ * between dequant and the inverse transform (TEST INFRASTRUCTURE ONLY; the two helpers PINNED slot by slot, the RECON walk, the chroma
+ * residual block and the scale pass PINNED on whole pictures against ff_vvc_reconstruct, tests/test_ref_recon_cpu.py; orc_tab_fill_pass
+ * UNPINNED; see orc_common.h).
  *
  *  - ilfnst_transform          libavcodec/vvc/vvc_intra.c:65-127
  *  - derive_transform_type     libavcodec/vvc/vvc_intra.c:130-164

@@ -1,6 +1,7 @@
 /*
- * oracle/ref_shim_intra.c — the static functions of the reference's vvc_intra.c, made callable, and (second half of the file) the
- * slots that take a VVCLocalContext, called on real structs filled from the mirror context of include/vvc_mi355_ctx.h.
+ * oracle/ref_shim_intra.c — the static functions of the reference's vvc_intra.c, made callable, (second part of the file) the
+ * slots that take a VVCLocalContext, called on real structs filled from the mirror context of include/vvc_mi355_ctx.h, and (third part)
+ * ref_recon_picture: ff_vvc_reconstruct itself over a whole picture built from plain arrays.
  *
  * TEST INFRASTRUCTURE ONLY, second translation unit of oracle/_ref/libvvcref.so (see ref_shim.c).  The reference file is
  * compiled into this unit by the #include below, resolved at build time from the reference tree; its ten external names
@@ -423,4 +424,273 @@ REF_API int ref_left_available(const MirLocalContext *m, int x, int y, int targe
 {
     load_ctx(m);
     return ff_vvc_get_left_available(&lc, x, y, target_size, c_idx);
+}
+
+/* ------------------------------------------------------------------ the RECON walk of a whole picture: ff_vvc_reconstruct itself
+ *
+ * ref_recon_picture builds, from plain arrays, the objects the reference's RECON stage reads — SPS / PPS / picture header / one
+ * SliceContext per slice, the CTU table with CodingUnit and TransformUnit lists allocated through ff_refstruct_allocz (the reference
+ * frees them), and the tables the parser paints per coding unit (imf, imm, imtf, ipm, cpm) — and calls the reference's own
+ * ff_vvc_reconstruct (compiled into this unit as shimdup_reconstruct) for every CTU in raster order.  The planes are reconstructed in
+ * place; they hold the inter prediction where a unit is not intra.  The levels are copied: the reference transforms them in place.
+ *
+ * One slot of the table is replaced: intra.lmcs_scale_chroma becomes a callback that calls the real slot and then appends what the
+ * reference cached in lc->lmcs (x_vpdu, y_vpdu, chroma_scale) to the caller's log.
+ *
+ * Every member of the arrays is an int32 (addresses: uint64), so that a numpy record array mirrors them without padding rules.
+ * Returns what ff_vvc_reconstruct returned last (0), or -1 for a picture these objects cannot hold: a unit with ciip_flag
+ * (ff_vvc_predict_ciip needs the inter machinery), more than MIR_MAX_SLICES slices, a transform unit with more than three blocks,
+ * a block beyond 64 samples, a unit outside its CTU.
+ */
+#include "libavcodec/refstruct.h"
+
+#define MIR_MAX_SLICES 8
+typedef struct MirReconTb { int32_t c_idx, x0, y0, w, h, ts, has_coeffs, min_x, min_y, max_x, max_y, level_off; } MirReconTb;
+typedef struct MirReconTu { int32_t x0, y0, w, h, coded_flag[3], joint, first_tb, n_tbs; } MirReconTu;
+typedef struct MirReconCu {
+    int32_t x0, y0, w, h, pred_mode, tree_type, mode_y, mode_c;
+    int32_t ref_idx, mip_flag, mip_mode, mip_transposed, mip_chroma_direct, isp_type, num_isp, bdpcm[3];
+    int32_t lfnst_idx, apply_lfnst[3], mts_idx, sbt_flag, sbt_horizontal, sbt_pos, coded_flag, ciip_flag, qp[4];
+    int32_t first_tu, n_tus;
+} MirReconCu;
+typedef struct MirReconPic {
+    uint64_t plane[3];
+    uint64_t slice_idx, col_bd, row_bd;            /* int16 per CTB; uint16 per CTB column (+1) / row (+1) */
+    uint64_t slice_dep_quant, slice_lmcs_used;     /* int32 per slice */
+    uint64_t ctu_first_cu, cus, tus, tbs, levels;  /* int32 [n_ctb + 1]; MirReconCu / Tu / Tb arrays; int32 level arena */
+    uint64_t scale_log;                            /* int32 [scale_log_cap][3], or 0 */
+    int32_t  stride[3];
+    int32_t  width, height, bit_depth, chroma_format_idc, ctb_log2;
+    int32_t  wpp, collocated, mts_enabled, explicit_mts_intra, explicit_mts_inter;
+    int32_t  log2_transform_range, min_qp_prime_ts, joint_cbcr_sign, chroma_residual_scale;
+    int32_t  lmcs_min_bin_idx, lmcs_max_bin_idx, lmcs_pivot[17], lmcs_chroma_scale_coeff[16];
+    int32_t  n_slices, n_levels, scale_log_cap, n_scale_log;
+} MirReconPic;
+
+REF_API int ref_recon_layout(int what)
+{
+    switch (what) {
+    case 0:  return (int)sizeof(MirReconPic);
+    case 1:  return (int)sizeof(MirReconCu);
+    case 2:  return (int)sizeof(MirReconTu);
+    case 3:  return (int)sizeof(MirReconTb);
+    case 4:  return (int)offsetof(MirReconPic, stride);
+    case 5:  return (int)offsetof(MirReconPic, n_slices);
+    default: return -1;
+    }
+}
+
+static SliceContext         rc_sc[MIR_MAX_SLICES];
+static H266RawSliceHeader   rc_sh[MIR_MAX_SLICES];
+static H266RawPictureHeader rc_ph;
+static MirReconPic         *rc_pic;
+static void (*rc_real_scale)(VVCLocalContext *lc, int *dst, const int *coeff, int w, int h, int x0_cu, int y0_cu);
+
+static void rc_scale_hook(VVCLocalContext *l, int *dst, const int *coeff, int w, int h, int x0_cu, int y0_cu)
+{
+    int32_t *log = (int32_t *)(uintptr_t)rc_pic->scale_log;
+    rc_real_scale(l, dst, coeff, w, h, x0_cu, y0_cu);
+    if (log && rc_pic->n_scale_log < rc_pic->scale_log_cap) {
+        int32_t *e = log + 3 * rc_pic->n_scale_log;
+        e[0] = l->lmcs.x_vpdu;
+        e[1] = l->lmcs.y_vpdu;
+        e[2] = l->lmcs.chroma_scale;
+    }
+    rc_pic->n_scale_log++;                      /* counts on past the capacity: the caller sees that the log was too short */
+}
+
+static void rc_paint(uint8_t *tab, int pitch, const MirReconCu *m, int v)
+{
+    for (int y = m->y0 >> 2; y < (m->y0 + m->h + 3) >> 2; y++)
+        memset(tab + y * pitch + (m->x0 >> 2), v, (size_t)((m->w + 3) >> 2));
+}
+
+REF_API int ref_recon_picture(MirReconPic *p)
+{
+    const int ctb = 1 << p->ctb_log2, ncx = (p->width + ctb - 1) >> p->ctb_log2, ncy = (p->height + ctb - 1) >> p->ctb_log2;
+    const int pitch = (p->width + 3) >> 2, units = pitch * ((p->height + 3) >> 2);
+    const int hs = p->chroma_format_idc == 1 || p->chroma_format_idc == 2, vs = p->chroma_format_idc == 1;
+    const int32_t *first = (const int32_t *)(uintptr_t)p->ctu_first_cu;
+    const MirReconCu *cus = (const MirReconCu *)(uintptr_t)p->cus;
+    const MirReconTu *tus = (const MirReconTu *)(uintptr_t)p->tus;
+    const MirReconTb *tbs = (const MirReconTb *)(uintptr_t)p->tbs;
+    uint8_t *tabs = NULL;
+    int *levels = NULL;
+    CTU *ctus = NULL;
+    int ret = -1;
+
+    p->n_scale_log = 0;
+    if (p->n_slices < 1 || p->n_slices > MIR_MAX_SLICES || p->ctb_log2 < 5 || p->ctb_log2 > 7 || p->chroma_format_idc < 0 || p->chroma_format_idc > 3 ||
+        (p->bit_depth != 8 && p->bit_depth != 10 && p->bit_depth != 12))
+        return -1;
+
+    wire(0, 4, 4, NULL);
+    memset(&frame, 0, sizeof(frame));
+    memset(rc_sc, 0, sizeof(rc_sc));
+    memset(rc_sh, 0, sizeof(rc_sh));
+    memset(&rc_ph, 0, sizeof(rc_ph));
+    rc_pic = p;
+    fc.frame = &frame;
+    for (int c = 0; c < 3; c++) {
+        frame.data[c]     = (uint8_t *)(uintptr_t)p->plane[c];
+        frame.linesize[c] = p->stride[c];
+        sps.hshift[c]     = (uint8_t)(c ? hs : 0);
+        sps.vshift[c]     = (uint8_t)(c ? vs : 0);
+    }
+    sps.width = pps.width = (uint16_t)p->width;
+    sps.height = pps.height = (uint16_t)p->height;
+    sps.bit_depth            = (uint8_t)p->bit_depth;
+    sps.pixel_shift          = p->bit_depth > 8;
+    sps.qp_bd_offset         = (uint8_t)(6 * (p->bit_depth - 8));
+    sps.log2_transform_range = (uint8_t)p->log2_transform_range;
+    sps.ctb_log2_size_y      = (uint8_t)p->ctb_log2;
+    sps.ctb_size_y           = (uint8_t)ctb;
+    sps.min_cb_log2_size_y   = 2;
+    raw_sps.sps_chroma_format_idc                 = (uint8_t)p->chroma_format_idc;
+    raw_sps.sps_entropy_coding_sync_enabled_flag  = (uint8_t)p->wpp;
+    raw_sps.sps_chroma_vertical_collocated_flag   = (uint8_t)p->collocated;
+    raw_sps.sps_mts_enabled_flag                  = (uint8_t)p->mts_enabled;
+    raw_sps.sps_explicit_mts_intra_enabled_flag   = (uint8_t)p->explicit_mts_intra;
+    raw_sps.sps_explicit_mts_inter_enabled_flag   = (uint8_t)p->explicit_mts_inter;
+    raw_sps.sps_min_qp_prime_ts                   = (uint8_t)p->min_qp_prime_ts;
+    pps.min_cb_width  = (uint16_t)pitch;
+    pps.ctb_width     = (uint16_t)ncx;
+    pps.ctb_height    = (uint16_t)ncy;
+    pps.ctb_to_col_bd = (uint16_t *)(uintptr_t)p->col_bd;
+    pps.ctb_to_row_bd = (uint16_t *)(uintptr_t)p->row_bd;
+    rc_ph.ph_joint_cbcr_sign_flag       = (uint8_t)p->joint_cbcr_sign;
+    rc_ph.ph_chroma_residual_scale_flag = (uint8_t)p->chroma_residual_scale;
+    fc.ps.ph.r = &rc_ph;
+    fc.ps.lmcs.min_bin_idx = (uint8_t)p->lmcs_min_bin_idx;
+    fc.ps.lmcs.max_bin_idx = (uint8_t)p->lmcs_max_bin_idx;
+    for (int i = 0; i < 17; i++)
+        fc.ps.lmcs.pivot[i] = (uint16_t)p->lmcs_pivot[i];
+    for (int i = 0; i < 16; i++)
+        fc.ps.lmcs.chroma_scale_coeff[i] = (uint16_t)p->lmcs_chroma_scale_coeff[i];
+    for (int s = 0; s < p->n_slices; s++) {
+        rc_sc[s].sh.r = &rc_sh[s];
+        rc_sh[s].sh_dep_quant_used_flag = (uint8_t)((const int32_t *)(uintptr_t)p->slice_dep_quant)[s];
+        rc_sh[s].sh_lmcs_used_flag      = (uint8_t)((const int32_t *)(uintptr_t)p->slice_lmcs_used)[s];
+    }
+    fc.tab.slice_idx = (int16_t *)(uintptr_t)p->slice_idx;
+    ff_vvc_dsp_init(&fc.vvcdsp, p->bit_depth);
+    rc_real_scale = fc.vvcdsp.intra.lmcs_scale_chroma;
+    fc.vvcdsp.intra.lmcs_scale_chroma = rc_scale_hook;
+
+    tabs   = calloc(6, (size_t)units);
+    levels = malloc(sizeof(int) * (size_t)(p->n_levels > 0 ? p->n_levels : 1));
+    ctus   = calloc((size_t)(ncx * ncy), sizeof(*ctus));
+    if (!tabs || !levels || !ctus)
+        goto done;
+    memcpy(levels, (const void *)(uintptr_t)p->levels, sizeof(int) * (size_t)(p->n_levels > 0 ? p->n_levels : 0));
+    fc.tab.imf  = tabs;
+    fc.tab.imm  = tabs + units;
+    fc.tab.imtf = tabs + 2 * units;
+    fc.tab.ipm  = tabs + 3 * units;
+    fc.tab.cpm[0] = tabs + 4 * units;
+    fc.tab.cpm[1] = tabs + 5 * units;
+    fc.tab.ctus = ctus;
+
+    /* the units: lists per CTU, and what the parser paints per unit (set_cu_tabs, vvc_ctu.c) */
+    for (int rs = 0; rs < ncx * ncy; rs++) {
+        CodingUnit **link = &ctus[rs].cus;
+        for (int i = first[rs]; i < first[rs + 1]; i++) {
+            const MirReconCu *m = &cus[i];
+            CodingUnit *u;
+            TransformUnit **tlink;
+            if (m->ciip_flag || m->n_tus < 0 || m->w < 1 || m->h < 1 || m->x0 < 0 || m->y0 < 0 || m->x0 + m->w > p->width || m->y0 + m->h > p->height ||
+                (m->x0 >> p->ctb_log2) != rs % ncx || (m->y0 >> p->ctb_log2) != rs / ncx || m->w > ctb || m->h > ctb)
+                goto done;
+            u = ff_refstruct_allocz(sizeof(*u));
+            if (!u)
+                goto done;
+            *link = u;
+            link = &u->next;
+            u->tree_type = m->tree_type == 1 ? DUAL_TREE_LUMA : m->tree_type == 2 ? DUAL_TREE_CHROMA : SINGLE_TREE;
+            u->ch_type   = m->tree_type == 2;
+            u->x0 = m->x0; u->y0 = m->y0; u->cb_width = m->w; u->cb_height = m->h;
+            u->pred_mode  = m->pred_mode ? MODE_INTRA : MODE_INTER;
+            u->coded_flag = (uint8_t)m->coded_flag;
+            u->sbt_flag = (uint8_t)m->sbt_flag; u->sbt_horizontal_flag = (uint8_t)m->sbt_horizontal; u->sbt_pos_flag = (uint8_t)m->sbt_pos;
+            u->lfnst_idx = m->lfnst_idx;
+            u->mts_idx   = (MtsIdx)m->mts_idx;
+            u->intra_luma_ref_idx = (uint8_t)m->ref_idx;
+            u->intra_mip_flag     = (uint8_t)m->mip_flag;
+            u->isp_split_type     = m->isp_type == 1 ? ISP_HOR_SPLIT : m->isp_type == 2 ? ISP_VER_SPLIT : ISP_NO_SPLIT;
+            u->num_intra_subpartitions = m->num_isp;
+            u->intra_pred_mode_y  = m->mode_y;
+            u->intra_pred_mode_c  = m->mode_c;
+            u->mip_chroma_direct_flag = m->mip_chroma_direct;
+            for (int c = 0; c < 3; c++) {
+                u->bdpcm_flag[c]       = m->bdpcm[c];
+                u->apply_lfnst_flag[c] = m->apply_lfnst[c];
+            }
+            for (int k = 0; k < 4; k++)
+                u->qp[k] = (int8_t)m->qp[k];
+            if (m->tree_type != 2) {
+                rc_paint(fc.tab.imf, pitch, m, m->mip_flag);
+                rc_paint(fc.tab.imm, pitch, m, m->mip_mode);
+                rc_paint(fc.tab.imtf, pitch, m, m->mip_transposed);
+                rc_paint(fc.tab.ipm, pitch, m, m->mode_y);
+                rc_paint(fc.tab.cpm[0], pitch, m, u->pred_mode);
+            }
+            if (m->tree_type != 1)
+                rc_paint(fc.tab.cpm[1], pitch, m, u->pred_mode);
+            tlink = &u->tus.head;
+            for (int j = m->first_tu; j < m->first_tu + m->n_tus; j++) {
+                const MirReconTu *mt = &tus[j];
+                TransformUnit *t;
+                if (mt->n_tbs < 0 || mt->n_tbs > VVC_MAX_SAMPLE_ARRAYS)
+                    goto done;
+                t = ff_refstruct_allocz(sizeof(*t));
+                if (!t)
+                    goto done;
+                *tlink = t;
+                tlink = &t->next;
+                u->tus.tail = t;
+                t->x0 = mt->x0; t->y0 = mt->y0; t->width = mt->w; t->height = mt->h;
+                t->joint_cbcr_residual_flag = (uint8_t)mt->joint;
+                for (int c = 0; c < 3; c++)
+                    t->coded_flag[c] = (uint8_t)mt->coded_flag[c];
+                t->nb_tbs = (uint8_t)mt->n_tbs;
+                for (int k = 0; k < mt->n_tbs; k++) {
+                    const MirReconTb *mb = &tbs[mt->first_tb + k];
+                    TransformBlock *b = &t->tbs[k];
+                    if (mb->w < 1 || mb->h < 1 || mb->w > 64 || mb->h > 64 || mb->c_idx < 0 || mb->c_idx > 2 ||
+                        (mb->has_coeffs && ((mb->w & (mb->w - 1)) || (mb->h & (mb->h - 1)))) ||         /* the uncoded part of an SBT unit may be 3/4 of a side */
+                        mb->level_off < 0 || mb->level_off + mb->w * mb->h > p->n_levels || mb->max_x >= mb->w || mb->max_y >= mb->h || mb->min_x < 0 || mb->min_y < 0)
+                        goto done;
+                    b->has_coeffs = (uint8_t)mb->has_coeffs;
+                    b->c_idx = (uint8_t)mb->c_idx;
+                    b->ts    = (uint8_t)mb->ts;
+                    b->x0 = mb->x0; b->y0 = mb->y0;
+                    b->tb_width = mb->w; b->tb_height = mb->h;
+                    b->log2_tb_width = av_log2(mb->w); b->log2_tb_height = av_log2(mb->h);
+                    b->min_scan_x = mb->min_x; b->min_scan_y = mb->min_y; b->max_scan_x = mb->max_x; b->max_scan_y = mb->max_y;
+                    b->coeffs = levels + mb->level_off;
+                }
+            }
+        }
+    }
+
+    ret = 0;
+    for (int rs = 0; rs < ncx * ncy && !ret; rs++) {
+        const int s = fc.tab.slice_idx[rs];
+        if (s < 0 || s >= p->n_slices) {
+            ret = -1;
+            break;
+        }
+        lc.sc = &rc_sc[s];
+        ret = shimdup_reconstruct(&lc, rs, rs % ncx, rs / ncx);
+    }
+
+done:
+    if (ctus)
+        for (int rs = 0; rs < ncx * ncy; rs++)
+            ff_vvc_ctu_free_cus(&ctus[rs]);
+    free(ctus);
+    free(levels);
+    free(tabs);
+    rc_pic = NULL;
+    return ret;
 }

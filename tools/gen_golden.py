@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/ref_slots.json, tests/golden/ref_passes.json and tests/golden/ref_inter.json: SHA-256 digests of what the
-reference's own C path computes on the case lists of tests/ref_cases.py, of what its in-loop filter callers compute on the pictures of
-tests/ref_pass_cases.py, and of what its inter prediction callers compute on the pictures of tests/ref_inter_cases.py.
+"""Regenerate tests/golden/ref_slots.json, tests/golden/ref_passes.json, tests/golden/ref_inter.json and tests/golden/ref_recon.json: SHA-256
+digests of what the reference's own C path computes on the case lists of tests/ref_cases.py, of what its in-loop filter callers compute on
+the pictures of tests/ref_pass_cases.py, of what its inter prediction callers compute on the pictures of tests/ref_inter_cases.py, and of what
+ff_vvc_reconstruct computes on the pictures of tests/ref_recon_cases.py.
 
 Needs oracle/_ref/libvvcref.so (`make -C oracle ref`, or __graft_entry__.build() where the reference tree is present).
 For every group of at most 64 cases (slot, bit depth, table indices) the file holds [digest of the concatenated inputs,
@@ -11,6 +12,8 @@ ref_passes.json holds per picture one digest of the inputs, one per output table
 ref_inter.json holds per picture one digest of the inputs and one per output plane; regular pictures add tab_dmvr_mvf, CIIP pictures the
 scratch, the intra weights and the patched .joint bytes; same rule.  Its digests are layout-independent: planes cropped to their width,
 MvField entries with the pad bytes zeroed.
+ref_recon.json holds per picture one digest of the inputs, one per plane after ff_vvc_reconstruct and one of the chroma scales the reference
+cached for the 64x64 units whose blocks the host routes to the TB passes; same rule.
 Usage: python tools/gen_golden.py [--check | --replace]"""
 import hashlib
 import json
@@ -37,6 +40,11 @@ try:                  # ... or no inter prediction pictures yet (ref_inter.json 
     import ref_inter_cases  # noqa: E402
 except ImportError:
     ref_inter_cases = None
+
+try:                  # ... or no RECON pictures yet (ref_recon.json is then left alone)
+    import ref_recon_cases  # noqa: E402
+except ImportError:
+    ref_recon_cases = None
 
 CONTEXT_SLOTS_AFTER = "ilfnst_transform"          # the context slots follow vvc_intra.c's static functions in the file
 
@@ -129,6 +137,15 @@ def generate_inter(lib):
             "pictures": {name: ref_inter_cases.host_digests(lib, "ref", name) for name in ref_inter_cases.picture_names()}}
 
 
+def generate_recon(lib):
+    """The document of ref_recon.json: the reference's RECON walk over whole pictures (ref_recon_picture of oracle/ref_shim_intra.c); nothing
+    of the oracle's enters the file."""
+    return {"source": "reference RECON stage (ff_vvc_reconstruct per CTU) through oracle/ref_shim_intra.c on tests/ref_recon_cases.py",
+            "format": "pictures[name][key] = sha256: inputs; the planes after reconstruction (p + component); scale = (unit x, unit y, chroma scale) of "
+                      "the 64x64 units whose blocks go to the TB passes, as the reference cached them",
+            "pictures": {name: ref_recon_cases.reference_digests(lib, name) for name in ref_recon_cases.picture_names()}}
+
+
 def changed_digests(old, new):
     """Groups of `old` that `new` drops or records differently: [] when `new` only adds to `old`."""
     return [f"{slot}/{key}" for slot, grp in old.items() for key, rec in grp.items() if new.get(slot, {}).get(key) != rec]
@@ -143,8 +160,10 @@ def main():
     p_path = ref_pass_cases.GOLDEN_PATH
     inter = dumps_passes(generate_inter(lib)) if ref_inter_cases is not None else None
     i_path = ref_inter_cases.GOLDEN_PATH if ref_inter_cases is not None else None
+    recon = dumps_passes(generate_recon(lib)) if ref_recon_cases is not None else None
+    r_path = ref_recon_cases.GOLDEN_PATH if ref_recon_cases is not None else None
     if "--check" in sys.argv:
-        for path, want in ((PATH, text), (p_path, passes), (i_path, inter)):
+        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon)):
             if path is None:
                 continue
             if not os.path.exists(path):
@@ -158,6 +177,8 @@ def main():
         bad += changed_digests(ref_pass_cases.load_golden(), json.loads(passes)["pictures"]) if os.path.exists(p_path) else []
         if i_path and os.path.exists(i_path):
             bad += changed_digests(ref_inter_cases.load_golden(), json.loads(inter)["pictures"])
+        if r_path and os.path.exists(r_path):
+            bad += changed_digests(ref_recon_cases.load_golden(), json.loads(recon)["pictures"])
         if bad:
             sys.exit(f"{len(bad)} recorded groups would change or vanish (first: {bad[:4]}): nothing written; --replace if that is meant")
     with open(PATH, "w") as f:
@@ -171,6 +192,10 @@ def main():
         with open(i_path, "w") as f:
             f.write(inter)
         print(f"wrote {i_path}: {len(json.loads(inter)['pictures'])} pictures, {len(inter)} bytes")
+    if r_path:
+        with open(r_path, "w") as f:
+            f.write(recon)
+        print(f"wrote {r_path}: {len(json.loads(recon)['pictures'])} pictures, {len(recon)} bytes")
 
 
 if __name__ == "__main__":
