@@ -823,6 +823,346 @@ __global__ __launch_bounds__(256) void deblock_kernel(const vvc355_deblock_job *
                                gld<uint8_t>(&jp->max_len_q[seg]));
 }
 
+// ---- packed 16-bit form of a segment, for the picture pass at BD <= 10.  A register holds one tap of TWO lines (the SAO helpers
+// above: pk16, pk_min / pk_max), so a tap of the 4-line segment is a register pair: [0] = lines (0, 1), [1] = lines (2, 3), the even
+// line in the low half.  That is what the horizontal pass loads (the four lines of a tap row are consecutive in memory: one 8-byte
+// load at 10 bits, one v_perm per register to widen 8-bit samples); the vertical pass loads four taps of a line and pairs the
+// lines with one v_perm per register.  The decisions read lines 0 and 3 (0 and 1 of a 2-line chroma segment): one more v_perm per
+// tap puts those two into one register, and every d2 / abs term is then computed once for both lines.  The filters run on both
+// register pairs and write the new taps over the old ones; store() then writes taps [0, np) and [0, nq) — the ones the segment's
+// filter class may modify, never another one: the lanes of the neighbouring edges own those in the same launch.
+//
+// Ranges with samples <= 1023 and tc <= 395 (Table 43's largest entry, reached at 10 bits), all within signed 16 bits unless noted:
+//   strong / chroma sums <= 8 * 1023 + 4 = 8188; the long filters' middle sum <= 16 * 1023 + 8 = 16376
+//   weak delta before the shift: |9 * (q0 - p0) - 3 * (q1 - p1) + 8| <= 12 * 1023 + 8 = 12284; 10 * tc <= 3950; 3 * tc <= 1185
+//   long filter: m * wt + ref * (64 - wt) + 32 <= 1023 * 64 + 32 = 65504: UNSIGNED 16-bit multiply-add and logical shift, only the
+//   difference to the old tap after it is signed (|.| <= 1023)
+typedef unsigned short upk16 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ upk16 upk(pk16 v) { return __builtin_bit_cast(upk16, v); }
+__device__ __forceinline__ upk16 upk_splat(int v) { return upk16{ (unsigned short)v, (unsigned short)v }; }
+__device__ __forceinline__ pk16 pk_abs(pk16 v) { return pk_max(v, pk_splat(0) - v); }
+__device__ __forceinline__ pk16 pk_clip(pk16 v, pk16 lo, pk16 hi) { return pk_max(pk_min(v, hi), lo); }
+__device__ __forceinline__ pk16 pk_clip_sym(pk16 v, int lim) { return pk_clip(v, pk_splat(-lim), pk_splat(lim)); }
+__device__ __forceinline__ pk16 pk_sel(bool c, pk16 a, pk16 b) { return pk(c ? un(a) : un(b)); }
+__device__ __forceinline__ pk16 pk_d2(pk16 a, pk16 b, pk16 c) { return pk_abs(a - b - b + c); }
+__device__ __forceinline__ pk16 pk_sar(pk16 v, int n) { return v >> pk_splat(n); }
+__device__ __forceinline__ uint32_t opaque(uint32_t v) { asm("" : "+v"(v)); return v; }
+__device__ __forceinline__ int pk_lo(pk16 v) { return v.x; }
+__device__ __forceinline__ int pk_hi(pk16 v) { return v.y; }
+
+template <int BD> struct DbkPk {
+    using px_t = typename Px<BD>::type;
+    uint8_t *pix;
+    int xs, ys, lines;                           // in pixels, as Dbk; lines = 4, or 2 (a chroma segment across a subsampled direction)
+    bool vert;                                   // the vertical pass: xs == 1
+    uint32_t P[8][2], Q[8][2];
+
+    // lines (0, 3) of a tap — (0, 1) of a 2-line segment — in one register
+    __device__ __forceinline__ pk16 dec(const uint32_t (&r)[2]) const
+    {
+        return pk(lines == 2 ? r[0] : __builtin_amdgcn_perm(r[1], r[0], 0x07060100u));
+    }
+    __device__ __forceinline__ void row(int o, uint32_t (&r)[2]) const
+    {
+        const px_t *a = (const px_t *)pix + o;
+        if (BD > 8) {
+            if (lines == 4) { const uint2 v = gld<uint2>(a); r[0] = v.x; r[1] = v.y; }
+            else { r[0] = gld<uint32_t>(a); r[1] = 0; }
+        } else {
+            const uint32_t v = lines == 4 ? gld<uint32_t>(a) : (uint32_t)gld<uint16_t>(a);
+            r[0] = __builtin_amdgcn_perm(0, v, 0x0c010c00u); r[1] = __builtin_amdgcn_perm(0, v, 0x0c030c02u);
+        }
+    }
+    // taps [4 * half, 4 * half + 4) of the sides in `which` (1: p, 2: q, 3: both); the others are left as they are
+    __device__ __forceinline__ void load(int half, int which)
+    {
+        const int b = 4 * half;
+        if (vert) {
+#pragma unroll
+            for (int s = 0; s < 2; s++) {
+                if (!(which & (1 << s)))
+                    continue;
+                uint32_t L[4][2];                // a line's four samples: two dwords at 10 bits, one at 8
+#pragma unroll
+                for (int l = 0; l < 4; l++) {
+                    L[l][0] = L[l][1] = 0;
+                    if (l < lines) {
+                        const px_t *a = (const px_t *)pix + l * ys + (s ? b : -b - 4);
+                        if (BD > 8) { const uint2 v = gld<uint2>(a); L[l][0] = v.x; L[l][1] = v.y; }
+                        else L[l][0] = gld<uint32_t>(a);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+#pragma unroll
+                    for (int j = 0; j < 2; j++) {
+                        const uint32_t t = BD > 8 ? __builtin_amdgcn_perm(L[2 * j + 1][k >> 1], L[2 * j][k >> 1], (k & 1) ? 0x07060302u : 0x05040100u)
+                                                  : __builtin_amdgcn_perm(L[2 * j + 1][0], L[2 * j][0], 0x0c040c00u + k * 0x00010001u);
+                        if (s) Q[b + k][j] = t; else P[b + 3 - k][j] = t;
+                    }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if (which & 1) row(-(b + i + 1) * xs, P[b + i]);
+                if (which & 2) row((b + i) * xs, Q[b + i]);
+            }
+        }
+    }
+    __device__ __forceinline__ void put_row(int o, const uint32_t (&r)[2]) const
+    {
+        px_t *a = (px_t *)pix + o;
+        if (BD > 8) {
+            if (lines == 4) gst<uint2>(a, make_uint2(r[0], r[1])); else gst<uint32_t>(a, r[0]);
+        } else {
+            const uint32_t v = __builtin_amdgcn_perm(r[1], r[0], 0x06040200u);
+            if (lines == 4) gst<uint32_t>(a, v); else gst<uint16_t>(a, (uint16_t)v);
+        }
+    }
+    // two taps of line half `h` of their registers, `first` at the lower address
+    __device__ __forceinline__ void put_pair(int o, uint32_t first, uint32_t second, int h) const
+    {
+        px_t *a = (px_t *)pix + o;
+        if (BD > 8) gst<uint32_t>(a, __builtin_amdgcn_perm(second, first, h ? 0x07060302u : 0x05040100u));
+        else gst<uint16_t>(a, (uint16_t)__builtin_amdgcn_perm(second, first, h ? 0x0c0c0602u : 0x0c0c0400u));
+    }
+    // Write back taps [0, np) of the p side and [0, nq) of the q side.  Horizontal pass: a tap row is one store (8 bytes at 10
+    // bits and four lines).  Vertical pass: the taps of a line are consecutive, p[i + 1] below p[i]: pairs (p1, p0), (p3, p2), ...
+    // as one 4-byte store (the edge is at a multiple of 4 samples, so these are aligned), the odd tap at the far end on its own.
+    __device__ __forceinline__ void store(int np, int nq) const
+    {
+        if (!vert) {
+#pragma unroll
+            for (int i = 0; i < 7; i++) {
+                if (i < np) put_row(-(i + 1) * xs, P[i]);
+                if (i < nq) put_row(i * xs, Q[i]);
+            }
+            return;
+        }
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+            if (l >= lines)
+                continue;
+            const int j = l >> 1, h = l & 1;
+#pragma unroll
+            for (int i = 0; i < 7; i += 2) {
+                if (i + 1 < 7 && i + 1 < np) put_pair(l * ys - i - 2, P[i + 1][j], P[i][j], h);
+                else if (i < np) st_px<BD>(pix, l * ys - i - 1, h ? P[i][j] >> 16 : P[i][j] & 0xffff);
+                if (i + 1 < 7 && i + 1 < nq) put_pair(l * ys + i, Q[i][j], Q[i + 1][j], h);
+                else if (i < nq) st_px<BD>(pix, l * ys + i, h ? Q[i][j] >> 16 : Q[i][j] & 0xffff);
+            }
+        }
+    }
+};
+
+// tap i of line pair j of the segment d, in the three filter functions below
+#define PJ(i) pk(d.P[i][j])
+#define QJ(i) pk(d.Q[i][j])
+
+// dbk_luma_large on both register pairs; len_p, len_q in {3, 5, 7}.  Returns the taps it changed through np / nq.
+template <int BD>
+__device__ __forceinline__ void dbk_luma_large_pk(DbkPk<BD> &d, int tc, int len_p, int len_q, int &np, int &nq)
+{
+    static_assert(BD <= 10, "the packed filters keep their intermediates in 16 bits: see the ranges above");
+#define MID(expr, sh) do { _Pragma("unroll") for (int j = 0; j < 2; j++) m[j] = pk_sar((expr) + pk_splat(1 << ((sh) - 1)), sh); } while (0)
+    pk16 m[2];
+    if (len_p == 5 && len_q == 5)
+        MID(PJ(4) + PJ(3) + (PJ(2) + PJ(1) + PJ(0) + QJ(0) + QJ(1) + QJ(2)) * pk_splat(2) + QJ(3) + QJ(4), 4);
+    else if (len_p == len_q)
+        MID(PJ(6) + PJ(5) + PJ(4) + PJ(3) + PJ(2) + PJ(1) + (PJ(0) + QJ(0)) * pk_splat(2) + QJ(1) + QJ(2) + QJ(3) + QJ(4) + QJ(5) + QJ(6), 4);
+    else if (len_p + len_q == 12)
+        MID(PJ(5) + PJ(4) + PJ(3) + PJ(2) + (PJ(1) + PJ(0) + QJ(0) + QJ(1)) * pk_splat(2) + QJ(2) + QJ(3) + QJ(4) + QJ(5), 4);
+    else if (len_p + len_q == 8)
+        MID(PJ(3) + PJ(2) + PJ(1) + PJ(0) + QJ(0) + QJ(1) + QJ(2) + QJ(3), 3);
+    else if (len_q == 7)
+        MID((PJ(2) + PJ(1) + PJ(0) + QJ(0)) * pk_splat(2) + PJ(0) + PJ(1) + QJ(1) + QJ(2) + QJ(3) + QJ(4) + QJ(5) + QJ(6), 4);
+    else
+        MID(PJ(6) + PJ(5) + PJ(4) + PJ(3) + PJ(2) + PJ(1) + (QJ(2) + QJ(1) + QJ(0) + PJ(0)) * pk_splat(2) + QJ(0) + QJ(1), 4);
+    np = len_p == 3 ? 3 : len_p == 5 ? 5 : 7;
+    nq = len_q == 3 ? 3 : len_q == 5 ? 5 : 7;
+    pk16 ref_p[2], ref_q[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        // selects between VALUES, as Dbk::p_at: folded back into one load from a selected address they would put P and Q into scratch
+        const uint32_t p32 = opaque(un(PJ(3) + PJ(2))), p54 = opaque(un(PJ(5) + PJ(4))), p76 = opaque(un(PJ(7) + PJ(6)));
+        const uint32_t q32 = opaque(un(QJ(3) + QJ(2))), q54 = opaque(un(QJ(5) + QJ(4))), q76 = opaque(un(QJ(7) + QJ(6)));
+        const uint32_t sp = len_p == 3 ? p32 : len_p == 5 ? p54 : p76;
+        const uint32_t sq = len_q == 3 ? q32 : len_q == 5 ? q54 : q76;
+        ref_p[j] = pk_sar(pk(sp) + pk_splat(1), 1);
+        ref_q[j] = pk_sar(pk(sq) + pk_splat(1), 1);
+    }
+    // (m * wt + ref * (64 - wt) + 32) >> 6 reaches 65504: unsigned
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+        if (i < np) {
+            const int lim = (tc * long_t(np, i)) >> 1, wt = long_w(np, i);
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const upk16 v = (upk(m[j]) * upk_splat(wt) + upk(ref_p[j]) * upk_splat(64 - wt) + upk_splat(32)) >> upk_splat(6);
+                d.P[i][j] = un(PJ(i) + pk_clip_sym(__builtin_bit_cast(pk16, v) - PJ(i), lim));
+            }
+        }
+        if (i < nq) {
+            const int lim = (tc * long_t(nq, i)) >> 1, wt = long_w(nq, i);
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const upk16 v = (upk(m[j]) * upk_splat(wt) + upk(ref_q[j]) * upk_splat(64 - wt) + upk_splat(32)) >> upk_splat(6);
+                d.Q[i][j] = un(QJ(i) + pk_clip_sym(__builtin_bit_cast(pk16, v) - QJ(i), lim));
+            }
+        }
+    }
+#undef MID
+}
+
+// dbk_luma_segment with no_p = no_q = 0 (the picture pass has no such samples): decisions on the (line 0, line 3) registers,
+// filters on both line pairs, the changed taps written over the old ones and counted in np / nq for DbkPk::store
+template <int BD>
+__device__ __forceinline__ void dbk_luma_segment_pk(DbkPk<BD> &d, int tc_in, int beta_in, int len_p, int len_q, int hor_ctu_edge, int &np, int &nq)
+{
+    static_assert(BD <= 10, "the packed filters keep their intermediates in 16 bits: see the ranges above");
+    np = nq = 0;
+    const int tc = BD < 10 ? (tc_in + (1 << (9 - BD))) >> (10 - BD) : tc_in << (BD - 10);
+    if (!tc)
+        return;
+    const pk16 p0 = d.dec(d.P[0]), p1 = d.dec(d.P[1]), p2 = d.dec(d.P[2]), p3 = d.dec(d.P[3]);
+    const pk16 q0 = d.dec(d.Q[0]), q1 = d.dec(d.Q[1]), q2 = d.dec(d.Q[2]), q3 = d.dec(d.Q[3]);
+    const pk16 dp = pk_d2(p2, p1, p0), dq = pk_d2(q2, q1, q0), dd = dp + dq;      // low half: line 0, high half: line 3
+    const pk16 apq = pk_abs(p0 - q0);
+    const int tc25 = (tc * 5 + 1) >> 1;
+    const int large_p = len_p > 3 && !hor_ctu_edge, large_q = len_q > 3;
+    const int beta = beta_in << (BD - 8);
+
+    if (large_p || large_q) {
+        const pk16 p4 = d.dec(d.P[4]), p5 = d.dec(d.P[5]), p6 = d.dec(d.P[6]), p7 = d.dec(d.P[7]);
+        const pk16 q4 = d.dec(d.Q[4]), q5 = d.dec(d.Q[5]), q6 = d.dec(d.Q[6]), q7 = d.dec(d.Q[7]);
+        const pk16 dpl = pk_sel(large_p, pk_sar(dp + pk_d2(p5, p4, p3) + pk_splat(1), 1), dp);
+        const pk16 dql = pk_sel(large_q, pk_sar(dq + pk_d2(q5, q4, q3) + pk_splat(1), 1), dq);
+        const pk16 ddl = dpl + dql;
+        const int beta53 = (beta * 3) >> 5, beta_4 = beta >> 4;
+        len_p = large_p ? len_p : 3;
+        len_q = large_q ? len_q : 3;
+        if (pk_lo(ddl) + pk_hi(ddl) < beta) {
+            const pk16 spl = pk_abs(p3 - p0) + pk_sel(len_p == 7, pk_abs(p7 - p6 - p5 + p4), pk_splat(0));
+            const pk16 sql = pk_abs(q0 - q3) + pk_sel(len_q == 7, pk_abs(q4 - q5 - q6 + q7), pk_splat(0));
+            const pk16 p_at = pk_sel(len_p == 7, p7, pk_sel(len_p == 5, p5, p3)), q_at = pk_sel(len_q == 7, q7, pk_sel(len_q == 5, q5, q3));
+            const pk16 sp = pk_sel(large_p, pk_sar(spl + pk_abs(p3 - p_at) + pk_splat(1), 1), spl);
+            const pk16 sq = pk_sel(large_q, pk_sar(sql + pk_abs(q3 - q_at) + pk_splat(1), 1), sql);
+            const pk16 s = sp + sq;
+            if (pk_lo(s) < beta53 && pk_lo(apq) < tc25 && pk_hi(s) < beta53 && pk_hi(apq) < tc25 &&
+                (pk_lo(ddl) << 1) < beta_4 && (pk_hi(ddl) << 1) < beta_4) {
+                dbk_luma_large_pk<BD>(d, tc, len_p, len_q, np, nq);
+                return;
+            }
+        }
+    }
+    if (pk_lo(dd) + pk_hi(dd) >= beta)
+        return;
+    const int beta_3 = beta >> 3, beta_2 = beta >> 2;
+    const pk16 s3 = pk_abs(p3 - p0) + pk_abs(q3 - q0);
+    if (len_p > 2 && len_q > 2 &&
+        pk_lo(s3) < beta_3 && pk_lo(apq) < tc25 && pk_hi(s3) < beta_3 && pk_hi(apq) < tc25 &&
+        (pk_lo(dd) << 1) < beta_2 && (pk_hi(dd) << 1) < beta_2) {
+        // strong filter, h2656_deblock_template.c:25
+        const int tc2 = tc << 1, tc3 = tc * 3;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const pk16 P3 = PJ(3), P2 = PJ(2), P1 = PJ(1), P0 = PJ(0), Q0 = QJ(0), Q1 = QJ(1), Q2 = QJ(2), Q3 = QJ(3);
+            const pk16 mid = P0 + Q0, two = pk_splat(2), four = pk_splat(4);
+            d.P[0][j] = un(P0 + pk_clip_sym(pk_sar(P2 + (P1 + mid) * two + Q1 + four, 3) - P0, tc3));
+            d.P[1][j] = un(P1 + pk_clip_sym(pk_sar(P2 + P1 + mid + two, 2) - P1, tc2));
+            d.P[2][j] = un(P2 + pk_clip_sym(pk_sar(P3 * two + P2 * pk_splat(3) + P1 + mid + four, 3) - P2, tc));
+            d.Q[0][j] = un(Q0 + pk_clip_sym(pk_sar(P1 + (mid + Q1) * two + Q2 + four, 3) - Q0, tc3));
+            d.Q[1][j] = un(Q1 + pk_clip_sym(pk_sar(mid + Q1 + Q2 + two, 2) - Q1, tc2));
+            d.Q[2][j] = un(Q2 + pk_clip_sym(pk_sar(Q3 * two + Q2 * pk_splat(3) + Q1 + mid + four, 3) - Q2, tc));
+        }
+        np = nq = 3;
+    } else {
+        // weak filter, h2656_deblock_template.c:52.  A line with abs(delta) >= 10 * tc is skipped: that half keeps its old taps,
+        // which are written back with the others (they are this segment's own)
+        np = nq = 1;
+        if (len_p > 1 && len_q > 1) {
+            const int side = (beta + (beta >> 1)) >> 3;
+            if (pk_lo(dp) + pk_hi(dp) < side) np = 2;
+            if (pk_lo(dq) + pk_hi(dq) < side) nq = 2;
+        }
+        const int tc_2 = tc >> 1;
+        const pk16 zero = pk_splat(0), top = pk_splat((1 << BD) - 1), one = pk_splat(1);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const pk16 P2 = PJ(2), P1 = PJ(1), P0 = PJ(0), Q0 = QJ(0), Q1 = QJ(1), Q2 = QJ(2);
+            const pk16 raw = pk_sar((Q0 - P0) * pk_splat(9) - (Q1 - P1) * pk_splat(3) + pk_splat(8), 4);
+            const uint32_t keep = un(pk_sar(pk_abs(raw) - pk_splat(10 * tc), 15));            // 0xffff where the line is filtered
+            const pk16 delta = pk_clip_sym(raw, tc);
+            const pk16 n_p0 = pk_clip(P0 + delta, zero, top), n_q0 = pk_clip(Q0 - delta, zero, top);
+            const pk16 n_p1 = pk_clip(P1 + pk_clip_sym(pk_sar(pk_sar(P2 + P0 + one, 1) - P1 + delta, 1), tc_2), zero, top);
+            const pk16 n_q1 = pk_clip(Q1 + pk_clip_sym(pk_sar(pk_sar(Q2 + Q0 + one, 1) - Q1 - delta, 1), tc_2), zero, top);
+            d.P[0][j] = (un(n_p0) & keep) | (d.P[0][j] & ~keep);
+            d.Q[0][j] = (un(n_q0) & keep) | (d.Q[0][j] & ~keep);
+            d.P[1][j] = (un(n_p1) & keep) | (d.P[1][j] & ~keep);
+            d.Q[1][j] = (un(n_q1) & keep) | (d.Q[1][j] & ~keep);
+        }
+    }
+}
+
+// dbk_chroma_segment with no_p = no_q = 0, on 2 or 4 lines
+template <int BD>
+__device__ __forceinline__ void dbk_chroma_segment_pk(DbkPk<BD> &d, int tc_in, int beta_in, int len_p, int len_q, int &np, int &nq)
+{
+    static_assert(BD <= 10, "the packed filters keep their intermediates in 16 bits: see the ranges above");
+    np = nq = 0;
+    const int tc = BD < 10 ? (tc_in + (1 << (9 - BD))) >> (10 - BD) : tc_in << (BD - 10);
+    if (!tc || !len_p || !len_q)
+        return;
+    const int beta = beta_in << (BD - 8), beta_3 = beta >> 3, beta_2 = beta >> 2, tc25 = (tc * 5 + 1) >> 1;
+    if (len_q == 3) {
+        const bool one = len_p == 1;
+        const pk16 p0 = d.dec(d.P[0]), p1 = d.dec(d.P[1]), p2 = pk_sel(one, p1, d.dec(d.P[2])), p3 = pk_sel(one, p1, d.dec(d.P[3]));
+        const pk16 q0 = d.dec(d.Q[0]), q1 = d.dec(d.Q[1]), q2 = d.dec(d.Q[2]), q3 = d.dec(d.Q[3]);
+        const pk16 dd = pk_d2(p2, p1, p0) + pk_d2(q2, q1, q0);                    // low half: line 0, high half: the last line
+        bool strong = false;
+        if (pk_lo(dd) + pk_hi(dd) < beta) {
+            const pk16 s3 = pk_abs(p3 - p0) + pk_abs(q0 - q3), apq = pk_abs(p0 - q0);
+            strong = (pk_lo(dd) << 1) < beta_2 && pk_lo(s3) < beta_3 && pk_lo(apq) < tc25 &&
+                     (pk_hi(dd) << 1) < beta_2 && pk_hi(s3) < beta_3 && pk_hi(apq) < tc25;
+        }
+        if (!strong)
+            len_p = len_q = 1;
+    }
+    const int kind = (len_p == 3 && len_q == 3) ? 2 : (len_q == 3) ? 1 : 0;
+    const pk16 t = pk_splat(tc), two = pk_splat(2), three = pk_splat(3), four = pk_splat(4);
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        if (2 * j >= d.lines)
+            continue;
+        const pk16 P3 = PJ(3), P2 = PJ(2), P1 = PJ(1), P0 = PJ(0), Q0 = QJ(0), Q1 = QJ(1), Q2 = QJ(2), Q3 = QJ(3);
+        if (kind == 2) {
+            d.P[0][j] = un(pk_clip(pk_sar(P3 + P2 + P1 + P0 * two + Q0 + Q1 + Q2 + four, 3), P0 - t, P0 + t));
+            d.P[1][j] = un(pk_clip(pk_sar(P3 * two + P2 + P1 * two + P0 + Q0 + Q1 + four, 3), P1 - t, P1 + t));
+            d.P[2][j] = un(pk_clip(pk_sar(P3 * three + P2 * two + P1 + P0 + Q0 + four, 3), P2 - t, P2 + t));
+        } else if (kind == 1) {
+            d.P[0][j] = un(pk_clip(pk_sar(P1 * three + P0 * two + Q0 + Q1 + Q2 + four, 3), P0 - t, P0 + t));
+        }
+        if (kind == 2) {
+            d.Q[0][j] = un(pk_clip(pk_sar(P2 + P1 + P0 + Q0 * two + Q1 + Q2 + Q3 + four, 3), Q0 - t, Q0 + t));
+        } else if (kind == 1) {
+            d.Q[0][j] = un(pk_clip(pk_sar(P1 * two + P0 + Q0 * two + Q1 + Q2 + Q3 + four, 3), Q0 - t, Q0 + t));
+        }
+        if (kind) {
+            d.Q[1][j] = un(pk_clip(pk_sar(P1 + P0 + Q0 + Q1 * two + Q2 + Q3 * two + four, 3), Q1 - t, Q1 + t));
+            d.Q[2][j] = un(pk_clip(pk_sar(P0 + Q0 + Q1 + Q2 * two + Q3 * three + four, 3), Q2 - t, Q2 + t));
+        } else {
+            const pk16 zero = pk_splat(0), top = pk_splat((1 << BD) - 1);
+            const pk16 delta = pk_clip_sym(pk_sar((Q0 - P0) * four + P1 - Q1 + four, 3), tc);
+            d.P[0][j] = un(pk_clip(P0 + delta, zero, top));
+            d.Q[0][j] = un(pk_clip(Q0 - delta, zero, top));
+        }
+    }
+    np = kind == 2 ? 3 : 1;
+    nq = kind ? 3 : 1;
+}
+#undef PJ
+#undef QJ
+
 // Table 43 (beta', tc' from Q), vvc_filter.c:38-52: generated from the reference's initialisers (tables_small.inc), the same text
 // tables.cpp exports as vvc355_tab_tc_table / _beta_table for the table check
 #define VVC355_TABLE(type, name, count) __device__ static const type lf_tab_##name[count]
@@ -890,7 +1230,7 @@ __global__ __launch_bounds__(256) void deblock_frame_kernel(const vvc355_deblock
         return;
     const uint32_t mine = slot[threadIdx.x];
     const bool is_chroma = mine >> 31;
-    // ---- phase B: the segment's parameters and the filter
+    // ---- phase B: the segment's parameters and the filter (up to 10 bits on packed samples, DbkPk; 12 bits on ints, Dbk)
     const int t = blockIdx.x * blockDim.x + (is_chroma ? (int)(mine & 255) : 0);
     const int unit = t >> 1;
     const int c = !is_chroma ? 0 : unit >= u2 ? 2 : 1;
@@ -932,9 +1272,26 @@ __global__ __launch_bounds__(256) void deblock_frame_kernel(const vvc355_deblock
         const int len_p = gld<uint8_t>((const uint8_t *)F.max_len_p + tu), len_q = gld<uint8_t>((const uint8_t *)F.max_len_q + tu);
         const int beta_offset = gld<int8_t>(dbp), tc_offset = gld<int8_t>(dbp + 3);
         int qp = (a + b + 1) >> 1;
+        DbkPk<BD> dk;                                  // (12 bits keep the int path and leave this unused)
+        if constexpr (BD <= 10) {
+            dk.pix = pix; dk.xs = xs; dk.ys = ys; dk.lines = 4; dk.vert = vertical;
+            dk.load(0, 3);
+#pragma unroll
+            for (int i = 4; i < 8; i++) dk.P[i][0] = dk.P[i][1] = dk.Q[i][0] = dk.Q[i][1] = 0;
+            const int far = (len_p > 3 && !hor_ctu_edge ? 1 : 0) | (len_q > 3 ? 2 : 0);
+            if (far)
+                dk.load(1, far);
+        }
         if (F.ladf_enabled) {
-            // lf.ladf_level (vvc_filter_template.c:788-803) and the interval search of get_qp_y (:840-846)
-            const int level = (ld_px<BD>(pix, -xs) + ld_px<BD>(pix, -xs + 3 * ys) + ld_px<BD>(pix, 0) + ld_px<BD>(pix, 3 * ys)) >> 2;
+            // lf.ladf_level (vvc_filter_template.c:788-803) and the interval search of get_qp_y (:840-846); the packed path has
+            // its four samples (p0 and q0 of lines 0 and 3) in registers already
+            int level;
+            if constexpr (BD <= 10) {
+                const pk16 s = dk.dec(dk.P[0]) + dk.dec(dk.Q[0]);
+                level = (pk_lo(s) + pk_hi(s)) >> 2;
+            } else {
+                level = (ld_px<BD>(pix, -xs) + ld_px<BD>(pix, -xs + 3 * ys) + ld_px<BD>(pix, 0) + ld_px<BD>(pix, 3 * ys)) >> 2;
+            }
             int qp_offset = F.ladf_lowest_qp_offset;
             bool go = true;                              // (no break: the loop must unroll so that the table indices are constants)
 #pragma unroll
@@ -947,7 +1304,13 @@ __global__ __launch_bounds__(256) void deblock_frame_kernel(const vvc355_deblock
         }
         const int beta = gld<uint8_t>(kBetaTable + clip3(qp + beta_offset, 0, 63));
         const int tc = gld<uint16_t>(kTcTable + clip3(qp + 2 * (bs - 1) + (tc_offset & -2), 0, 65));
-        deblock_luma_seg<BD>(pix, xs, ys, tc, beta, 0, 0, len_p, len_q, hor_ctu_edge);
+        if constexpr (BD <= 10) {
+            int np, nq;
+            dbk_luma_segment_pk<BD>(dk, tc, beta, len_p, len_q, hor_ctu_edge, np, nq);
+            dk.store(np, nq);
+        } else {
+            deblock_luma_seg<BD>(pix, xs, ys, tc, beta, 0, 0, len_p, len_q, hor_ctu_edge);
+        }
         return;
     }
     const int8_t *qc = (const int8_t *)(c == 1 ? F.qp_c[0] : F.qp_c[1]);
@@ -975,7 +1338,16 @@ __global__ __launch_bounds__(256) void deblock_frame_kernel(const vvc355_deblock
         const int beta_offset = gld<int8_t>(dbp + c), tc_offset = gld<int8_t>(dbp + 3 + c);
         const int beta = gld<uint8_t>(kBetaTable + clip3(qp + beta_offset, 0, 63));
         const int tc = gld<uint16_t>(kTcTable + clip3(qp + 2 * (bs - 1) + (tc_offset & -2), 0, 65));
-        deblock_chroma_seg<BD>(pix, xs, ys, lines, tc, beta, 0, 0, len_p, len_q);
+        if constexpr (BD <= 10) {
+            DbkPk<BD> dk;
+            dk.pix = pix; dk.xs = xs; dk.ys = ys; dk.lines = lines; dk.vert = vertical;
+            dk.load(0, 3);
+            int np, nq;
+            dbk_chroma_segment_pk<BD>(dk, tc, beta, len_p, len_q, np, nq);
+            dk.store(np, nq);
+        } else {
+            deblock_chroma_seg<BD>(pix, xs, ys, lines, tc, beta, 0, 0, len_p, len_q);
+        }
     }
 }
 
