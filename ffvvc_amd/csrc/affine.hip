@@ -18,6 +18,8 @@
 //    per sample: gradients, refinement, rounding or blending, the forward map, the store.
 // Three group synchronisations after the descriptor's, whatever the number of lists.
 #include "common.hpp"
+#include "pk16.hpp"
+#include "wave.hpp"
 #include "runtime.hpp"
 #include "../../include/vvc_mi355.h"
 
@@ -38,19 +40,6 @@ struct AffineLds {
 };
 static_assert(sizeof(AffineLds) % 16 == 0 && offsetof(AffineLds, win) % 8 == 0 && sizeof(uint16_t[11 * kAwP]) % 8 == 0, "8-byte window rows");
 
-__device__ __forceinline__ void group16_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-typedef short a_v2s __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int a_dot2(uint32_t a, uint32_t b, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(a_v2s, a), __builtin_bit_cast(a_v2s, b), acc, false);
-}
-__device__ __forceinline__ uint32_t a_pack16(int lo, int hi) { return (uint32_t)(lo & 0xffff) | ((uint32_t)hi << 16); }
-
 // Two adjacent outputs of an 8-tap filter from five aligned sample pairs d[m] = (p[2m], p[2m + 1]): out0 = sum f[k] p[k],
 // out1 = sum f[k] p[k + 1]; p[9] meets a zero.
 struct AffineTaps {
@@ -64,11 +53,11 @@ struct AffineTaps {
 #pragma unroll
         for (int k = 0; k < 8; k++) f[k] = (int)(int8_t)((k < 4 ? raw.x : raw.y) >> ((k & 3) * 8));
 #pragma unroll
-        for (int m = 0; m < 4; m++) e[m] = a_pack16(f[2 * m], f[2 * m + 1]);
-        o[0] = a_pack16(0, f[0]);
+        for (int m = 0; m < 4; m++) e[m] = pack16(f[2 * m], f[2 * m + 1]);
+        o[0] = pack16(0, f[0]);
 #pragma unroll
-        for (int m = 1; m < 4; m++) o[m] = a_pack16(f[2 * m - 1], f[2 * m]);
-        o[4] = a_pack16(f[7], 0);
+        for (int m = 1; m < 4; m++) o[m] = pack16(f[2 * m - 1], f[2 * m]);
+        o[4] = pack16(f[7], 0);
     }
     __device__ __forceinline__ void apply(const uint32_t *d, int &out0, int &out1) const
     {
@@ -77,9 +66,9 @@ struct AffineTaps {
         for (int m = 0; m < 5; m++) dd[m] = d[m];
         int a = 0, b = 0;
 #pragma unroll
-        for (int m = 0; m < 4; m++) a = a_dot2(dd[m], e[m], a);
+        for (int m = 0; m < 4; m++) a = dot2(dd[m], e[m], a);
 #pragma unroll
-        for (int m = 0; m < 5; m++) b = a_dot2(dd[m], o[m], b);
+        for (int m = 0; m < 5; m++) b = dot2(dd[m], o[m], b);
         out0 = a; out1 = b;
     }
 };
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void affine_kernel(const vvc355_affine_job *__
         L.job[l] = gld<uint32_t>(q + l);
         if (l < 8)
             L.job[16 + l] = gld<uint32_t>(q + 16 + l);
-        group16_sync();
+        wave_sync();
     }
     vvc355_affine_job job;
     __builtin_memcpy(&job, L.job, sizeof(job));
@@ -130,7 +119,7 @@ __global__ __launch_bounds__(256) void affine_kernel(const vvc355_affine_job *__
                         v[it] = gld<uint2>(p);
                     } else {
                         const uint32_t q = gld<uint32_t>(p);
-                        v[it] = make_uint2(__builtin_amdgcn_perm(0, q, 0x0c010c00u), __builtin_amdgcn_perm(0, q, 0x0c030c02u));
+                        v[it] = make_uint2(widen_lo(q), widen_hi(q));
                     }
                 }
             }
@@ -148,7 +137,7 @@ __global__ __launch_bounds__(256) void affine_kernel(const vvc355_affine_job *__
                 win[r * kAwP + c] = (uint16_t)gld<px_t>(plane + (ptrdiff_t)ya * stride + xa * (int)sizeof(px_t));
             }
         }
-        group16_sync();
+        wave_sync();
         // ---- put[LUMA][..] (h2656_inter_template.c:29, :97, :112, :127), horizontal: rows 0 .. 10, outputs 2 xp and 2 xp + 1
         AffineTaps t;
         t.set(mvx & 15);
@@ -160,7 +149,7 @@ __global__ __launch_bounds__(256) void affine_kernel(const vvc355_affine_job *__
             thT[(2 * xp) * kAtP + r] = (int16_t)(o0 >> (BD - 8));
             thT[(2 * xp + 1) * kAtP + r] = (int16_t)(o1 >> (BD - 8));
         }
-        group16_sync();
+        wave_sync();
         // ---- vertical: column x, rows 2 yp and 2 yp + 1; put stores int16
         if ((l >> 3) < nl) {
             const int x = l & 3, yp = (l >> 2) & 1;
@@ -189,7 +178,7 @@ __global__ __launch_bounds__(256) void affine_kernel(const vvc355_affine_job *__
             L.pp[s][(ry + 1) * 6 + rx + 1] = (int16_t)(v << (14 - BD));
         }
     }
-    group16_sync();
+    wave_sync();
     // ---- one lane per sample: the PROF gradients and refinement (:135, :160-235), then the output
     const int x = l & 3, y = l >> 2, o = (y + 1) * 6 + x + 1;
     int val[2] = { 0, 0 };

@@ -11,6 +11,7 @@
 // (the unit that shares a coefficient set), pulls its 10x12-sample window into registers with aligned
 // ds_read_b64, and classifies + filters from registers.  Rows next to the virtual boundary take a slower LDS path.
 #include "common.hpp"
+#include "pk16.hpp"
 #include "runtime.hpp"
 #include "../../include/vvc_mi355.h"
 
@@ -69,19 +70,6 @@ __device__ __forceinline__ int mad24(int f, int p, int acc)
 }
 
 // rows between row y and the virtual boundary on y's own side (0 = adjacent): taps fold to min(k, dist)
-// 8 consecutive samples as four registers of two 16-bit samples each, whatever the storage type
-template <int BD> __device__ __forceinline__ void load8_u16(const typename Px<BD>::type *p, uint32_t (&d)[4])
-{
-    if (BD > 8) {
-        const uint4 q = gld<uint4>(p);
-        d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
-    } else {
-        const uint2 q = gld<uint2>(p);
-        d[0] = __builtin_amdgcn_perm(0, q.x, 0x0c010c00u); d[1] = __builtin_amdgcn_perm(0, q.x, 0x0c030c02u);
-        d[2] = __builtin_amdgcn_perm(0, q.y, 0x0c010c00u); d[3] = __builtin_amdgcn_perm(0, q.y, 0x0c030c02u);
-    }
-}
-
 __device__ __forceinline__ int vb_dist(int y, int vb_pos) { return y < vb_pos ? vb_pos - 1 - y : y - vb_pos; }
 
 // ---------------------------------------------------------------------------------------------- tile staging
@@ -113,8 +101,8 @@ __device__ __forceinline__ void stage_tile(uint16_t (*tile)[TW], const vvc355_al
                 q = gld_at<uint4>(src_m, row_m + c0 * (int)sizeof(px_t));
             } else {
                 const uint2 t = gld_at<uint2>(src_m, row_m + c0);
-                q.x = __builtin_amdgcn_perm(0, t.x, 0x0c010c00u); q.y = __builtin_amdgcn_perm(0, t.x, 0x0c030c02u);
-                q.z = __builtin_amdgcn_perm(0, t.y, 0x0c010c00u); q.w = __builtin_amdgcn_perm(0, t.y, 0x0c030c02u);
+                q.x = widen_lo(t.x); q.y = widen_hi(t.x);
+                q.z = widen_lo(t.y); q.w = widen_hi(t.y);
             }
         } else {
             uint32_t v[8];
@@ -331,25 +319,11 @@ static constexpr int kCellCols = 34;                   // block columns -1 .. 32
 static constexpr int kCTileW   = 80;                   // 4:2:0 chroma strip: columns -8 .. 71
 static constexpr int kCTileH   = kStripH / 2 + 4;      // rows -2 .. 17
 
-typedef short alf_v2s __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int sdot2(uint32_t a, uint32_t b, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(alf_v2s, a), __builtin_bit_cast(alf_v2s, b), acc, false);
-}
-// (low half of a) | (low half of b) << 16, whatever the upper halves hold
-__device__ __forceinline__ uint32_t pk_ll(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
-// the same written so that wave-uniform operands stay on the scalar unit
-__device__ __forceinline__ uint32_t upk_ll(uint32_t a, uint32_t b) { return (a & 0xffffu) | (b << 16); }
-__device__ __forceinline__ uint32_t pk_l0(uint32_t a) { return a & 0xffffu; }
-__device__ __forceinline__ uint32_t pk_0l(uint32_t a) { return a << 16; }
-
 // One cell of the Laplacian grid (vvc_filter_template.c:325-343): samples A = (row 1, column ca) and B = (row 2, ca + 1) of four
 // rows given as dwords of two samples (even column in the low half): up = the row above A (A's own row at the virtual boundary,
 // :323-324), ra = A's row, rb = B's row, dn = the row below B (B's own row at the boundary, :321-322); u0 / a0 / b0 / d0 hold
 // columns ca-2 ca-1, *1 columns ca ca+1, *2 columns ca+2 ca+3.  A's term sits in the low half, B's in the high half of every
 // operand, so one v_sad_u16 per direction adds |2A - n1 - n2| + |2B - n1' - n2'|.  Returns V | H << 16 and D0 | D1 << 16.
-__device__ __forceinline__ uint32_t lo_hi(uint32_t lo_src, uint32_t hi_src) { return __builtin_amdgcn_perm(hi_src, lo_src, 0x07060100u); }    // lo(lo_src) | hi(hi_src)
-__device__ __forceinline__ uint32_t hi_lo(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040302u); }                       // hi(a) | lo(b) << 16
 __device__ __forceinline__ void grad_cell_pk(uint32_t u0, uint32_t u1, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1, uint32_t b2,
                                              uint32_t d1, uint32_t d2, uint32_t &vh, uint32_t &dd)
 {
@@ -405,19 +379,19 @@ __device__ __forceinline__ void filter_block_fast(const Win &win, const uint32_t
                 const int b0 = par ? m - 1 : m - 2, b2 = par ? m : m - 1;
                 int sum = dist == 0 ? 512 : 64;
 #pragma unroll
-                for (int q = 0; q < 4; q++) sum = sdot2(win.d[r0][b0 + q], z0[q], sum);
+                for (int q = 0; q < 4; q++) sum = dot2(win.d[r0][b0 + q], z0[q], sum);
 #pragma unroll
                 for (int q = 0; q < 3; q++) {
-                    sum = sdot2(win.d[r0 + d1][m - 1 + q], p1[q], sum);
-                    sum = sdot2(win.d[r0 - d1][m - 1 + q], m1[q], sum);
+                    sum = dot2(win.d[r0 + d1][m - 1 + q], p1[q], sum);
+                    sum = dot2(win.d[r0 - d1][m - 1 + q], m1[q], sum);
                 }
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
-                    sum = sdot2(win.d[r0 + d2][b2 + q], p2[q], sum);
-                    sum = sdot2(win.d[r0 - d2][b2 + q], m2[q], sum);
+                    sum = dot2(win.d[r0 + d2][b2 + q], p2[q], sum);
+                    sum = dot2(win.d[r0 - d2][b2 + q], m2[q], sum);
                 }
-                sum = sdot2(win.d[r0 + d3][m], p3, sum);
-                sum = sdot2(win.d[r0 - d3][m], p3, sum);
+                sum = dot2(win.d[r0 + d3][m], p3, sum);
+                sum = dot2(win.d[r0 - d3][m], p3, sum);
                 const int o = clip_px<BD>(dist == 0 ? sum >> 10 : sum >> 7);
                 outp[i][jj] = par ? outp[i][jj] | ((uint32_t)o << 16) : (uint32_t)o;
             }
@@ -429,7 +403,7 @@ __device__ __forceinline__ void filter_block_fast(const Win &win, const uint32_t
         if (BD > 8)
             gst<uint2>(d, make_uint2(outp[i][0], outp[i][1]));
         else
-            gst<uint32_t>(d, __builtin_amdgcn_perm(outp[i][1], outp[i][0], 0x06040200u));
+            gst<uint32_t>(d, narrow4(outp[i][0], outp[i][1]));
     }
 }
 
@@ -468,15 +442,15 @@ __device__ __forceinline__ void chroma_quad_fast(const uint32_t (&win)[5][4], co
         const int c = j + 2, m = c >> 1;
         int sum = dist == 0 ? 512 : 64;
         if (!(c & 1)) {                         // dwords m-1 (c-2 c-1), m (c c+1), m+1 (c+2 c+3)
-            sum = sdot2(win[2][m - 1], upk_ll(F4, F5), sum); sum = sdot2(win[2][m], ce, sum); sum = sdot2(win[2][m + 1], pk_l0(F4), sum);
-            sum = sdot2(win[3][m - 1], pk_0l(F3), sum); sum = sdot2(win[3][m], upk_ll(F2, F1), sum);
-            sum = sdot2(win[1][m - 1], pk_0l(F1), sum); sum = sdot2(win[1][m], upk_ll(F2, F3), sum);
-            sum = sdot2(win[4][m], pk_l0(F0), sum); sum = sdot2(win[0][m], pk_l0(F0), sum);
+            sum = dot2(win[2][m - 1], upk_ll(F4, F5), sum); sum = dot2(win[2][m], ce, sum); sum = dot2(win[2][m + 1], pk_l0(F4), sum);
+            sum = dot2(win[3][m - 1], pk_0l(F3), sum); sum = dot2(win[3][m], upk_ll(F2, F1), sum);
+            sum = dot2(win[1][m - 1], pk_0l(F1), sum); sum = dot2(win[1][m], upk_ll(F2, F3), sum);
+            sum = dot2(win[4][m], pk_l0(F0), sum); sum = dot2(win[0][m], pk_l0(F0), sum);
         } else {                                // dwords m-1 (c-3 c-2), m (c-1 c), m+1 (c+1 c+2)
-            sum = sdot2(win[2][m - 1], pk_0l(F4), sum); sum = sdot2(win[2][m], co, sum); sum = sdot2(win[2][m + 1], upk_ll(F5, F4), sum);
-            sum = sdot2(win[3][m], upk_ll(F3, F2), sum); sum = sdot2(win[3][m + 1], pk_l0(F1), sum);
-            sum = sdot2(win[1][m], upk_ll(F1, F2), sum); sum = sdot2(win[1][m + 1], pk_l0(F3), sum);
-            sum = sdot2(win[4][m], pk_0l(F0), sum); sum = sdot2(win[0][m], pk_0l(F0), sum);
+            sum = dot2(win[2][m - 1], pk_0l(F4), sum); sum = dot2(win[2][m], co, sum); sum = dot2(win[2][m + 1], upk_ll(F5, F4), sum);
+            sum = dot2(win[3][m], upk_ll(F3, F2), sum); sum = dot2(win[3][m + 1], pk_l0(F1), sum);
+            sum = dot2(win[1][m], upk_ll(F1, F2), sum); sum = dot2(win[1][m + 1], pk_l0(F3), sum);
+            sum = dot2(win[4][m], pk_0l(F0), sum); sum = dot2(win[0][m], pk_0l(F0), sum);
         }
         out[j] = clip_px<BD>(dist == 0 ? sum >> 10 : sum >> 7);
     }
@@ -734,12 +708,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
                 const uint32_t k_c0 = pk_0l(G1), k_c1 = pk_0l(G2), k_d0 = pk_0l(G3), k_d1 = upk_ll(G4, G5), k_u = pk_l0(G0), k_2 = pk_l0(G6);
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    int s = sdot2(lc[j], k_c0, 0);
-                    s = sdot2(lc[j + 1], k_c1, s);
-                    s = sdot2(ld[j], k_d0, s);
-                    s = sdot2(ld[j + 1], k_d1, s);
-                    s = sdot2(lu[j], k_u, s);
-                    s = sdot2(l2[j], k_2, s);
+                    int s = dot2(lc[j], k_c0, 0);
+                    s = dot2(lc[j + 1], k_c1, s);
+                    s = dot2(ld[j], k_d0, s);
+                    s = dot2(ld[j + 1], k_d1, s);
+                    s = dot2(lu[j], k_u, s);
+                    s = dot2(l2[j], k_2, s);
                     s = mad24(gcen, (int)(lc[j + 1] & 0xffff), s);
                     s = clip3((s + 64) >> 7, -(1 << (BD - 1)), (1 << (BD - 1)) - 1);
                     out[j] = clip_px<BD>(out[j] + s);
@@ -854,15 +828,15 @@ __global__ __launch_bounds__(256) void alf_cc_kernel(const vvc355_alf_job *__res
             up = max(ly + up, row_min) - ly; dn = min(ly + dn, row_max) - ly; dn2 = min(ly + dn2, row_max) - ly;
             const int left = (x | job.ext_l) ? 1 : 0;        // column -1 of the rectangle only where it is readable
             uint32_t ru[4], rc[4], rd[4], r2[4];
-            load8_u16<BD>(l0 + up * ls, ru);
-            load8_u16<BD>(l0, rc);
-            load8_u16<BD>(l0 + dn * ls, rd);
-            load8_u16<BD>(l0 + dn2 * ls, r2);
+            load8_pk<BD>(l0 + up * ls, ru);
+            load8_pk<BD>(l0, rc);
+            load8_pk<BD>(l0 + dn * ls, rd);
+            load8_pk<BD>(l0 + dn2 * ls, r2);
             const int ec = gld<px_t>(l0 - left), ed = gld<px_t>(l0 + dn * ls - left);
             uint8_t *d = (uint8_t *)job.dst + (ptrdiff_t)y * job.dst_stride + x * (int)sizeof(px_t);
             uint32_t cv[2];
             if (BD > 8) { const uint2 q = gld<uint2>(d); cv[0] = q.x; cv[1] = q.y; }
-            else { const uint32_t q = gld<uint32_t>(d); cv[0] = __builtin_amdgcn_perm(0, q, 0x0c010c00u); cv[1] = __builtin_amdgcn_perm(0, q, 0x0c030c02u); }
+            else { const uint32_t q = gld<uint32_t>(d); cv[0] = widen_lo(q); cv[1] = widen_hi(q); }
             int out[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {

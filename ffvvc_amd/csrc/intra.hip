@@ -9,6 +9,8 @@
 // lanes sweep the block row-major so that every row store is contiguous.
 #include <type_traits>
 #include "common.hpp"
+#include "pk16.hpp"
+#include "wave.hpp"
 #include "runtime.hpp"
 #include "resid_math.hpp"
 #include "../../include/vvc_mi355.h"
@@ -231,12 +233,6 @@ struct LTabsLane {                       // the same LDS copy read per lane (the
 // ------------------------------------------------------------------------------------------------ leaf predictors
 // Executed by a group of NT lanes (a wave or the whole workgroup); `tid` is the lane's index in its group.
 
-template <int NT> __device__ __forceinline__ void group_sync()
-{
-    if (NT <= 64) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }     // the group sits inside one wave
-    else __syncthreads();
-}
-
 template <int BD, int NT, typename R, typename PX>
 __device__ void pred_planar(int tid, PX src, int stride, R top, R left, int w, int h)
 {
@@ -254,10 +250,10 @@ __device__ void pred_planar(int tid, PX src, int stride, R top, R left, int w, i
 template <int NT> __device__ __forceinline__ int group_sum(int v, int tid, int *scratch)
 {
     if (NT <= 64) {
-        v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);      // row_shr:1
-        v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);      // row_shr:2
-        v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);      // row_shr:4
-        v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);      // row_shr:8
+        v += dpp0<kDppShr1>(v);
+        v += dpp0<kDppShr2>(v);
+        v += dpp0<kDppShr4>(v);
+        v += dpp0<kDppShr8>(v);
         const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31);
         const int r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
         if (NT == 64)
@@ -1329,9 +1325,6 @@ __global__ __launch_bounds__(256) void lmcs_vpdu_scale_kernel(const vvc355_lmcs_
         gst<int16_t>((int16_t *)f.scale + u, (int16_t)s);
 }
 
-// a value of lane `src` (any lane, per lane): ds_bpermute, every lane of the wave active
-__device__ __forceinline__ int lane_get(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
-
 // what the waves of a workgroup need of its 64 slots
 struct ResidSlots {
     int incl[64];               // units of slots 0 .. i: unit u belongs to the first slot whose entry exceeds u
@@ -1694,8 +1687,7 @@ __device__ __forceinline__ int recon_luma_done_get(ReconLds &L)
 __device__ __forceinline__ void recon_sync_mem()
 {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_sync();
 }
 
 // CTU body tiles: rows 0 .. ctb - 1, columns -kApr .. ctb - 1 (the left apron holds the left neighbour's last columns); strips: the
@@ -1719,7 +1711,7 @@ __device__ __forceinline__ uint2 recon_chunk_load(const uint8_t *plane, int stri
         if (BD > 8)
             return gld<uint2>(p);
         const uint32_t q = gld<uint32_t>(p);
-        return make_uint2(__builtin_amdgcn_perm(0, q, 0x0c010c00u), __builtin_amdgcn_perm(0, q, 0x0c030c02u));
+        return make_uint2(widen_lo(q), widen_hi(q));
     }
     uint32_t e[4];
 #pragma unroll
@@ -1805,7 +1797,7 @@ __device__ void recon_tile_store(const uint16_t *tile, int pitch, uint8_t *plane
         if (BD > 8)
             gst<uint2>(p, v);
         else
-            gst<uint32_t>(p, __builtin_amdgcn_perm(v.y, v.x, 0x06040200u));
+            gst<uint32_t>(p, narrow4(v.x, v.y));
     }
 }
 

@@ -9,6 +9,8 @@
 // pass spreads (column, output row) pairs over the lanes, then the row pass does the same for (row, output column).
 #include <type_traits>
 #include "common.hpp"
+#include "pk16.hpp"
+#include "wave.hpp"
 #include "runtime.hpp"
 #include "resid_math.hpp"
 #include "../../include/vvc_mi355.h"
@@ -215,12 +217,6 @@ __device__ __forceinline__ int4 lv_load4(const vvc355_tb_levels &r, const int16_
     return make_int4(v[0], v[1], v[2], v[3]);
 }
 
-#define ITX_SYNC()                                                                \
-    do {                                                                            \
-        if (WAVE) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } \
-        else __syncthreads();                                                       \
-    } while (0)
-
 // One transform block of any shape with w * h <= CAP, worked on by the NT lanes `tid` = 0..NT-1 of a group (NT <= 64: the
 // group sits inside one wave and synchronises at wave level; NT = 256: the whole workgroup).  buf / tmp: CAP ints of LDS each.
 // PACKED: the levels come from the side record `lvr` (groups in `levels`, or int32 at job.coeffs for VVC355_LEVELS_INT32).
@@ -285,7 +281,7 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
             }
         }
     }
-    ITX_SYNC();
+    group_sync<NT>();
 
     if constexpr (LFNST) {
         if (lf_idx) {
@@ -312,7 +308,7 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
                         t[q] += u * (unsigned)(int)m[i * n_out + j];
                 }
             }
-            ITX_SYNC();
+            group_sync<NT>();
 #pragma unroll
             for (int q = 0; q < MAXO; q++) {
                 const int j = tid + q * NT;
@@ -331,7 +327,7 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
                 }
             }
             nzw = nzh = big ? 8 : 4;
-            ITX_SYNC();
+            group_sync<NT>();
         }
     }
 
@@ -343,7 +339,7 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
         if (w == h && dc_only) {
             const int t = (buf[0] * 64 + (1 << (sh1 - 1))) >> sh1;
             const int dc = (t * 64 + (1 << (sh_final - 1))) >> sh_final;
-            ITX_SYNC();
+            group_sync<NT>();
             for (int i = tid; i < n; i += NT)
                 buf[i] = dc;
             sh_final = -1;
@@ -393,7 +389,7 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
                         tmp[x * h + y] = x < nzw ? clip_intp2((acc[q] + (1 << (sh1 - 1))) >> sh1, range) : 0;
                 }
             }
-            ITX_SYNC();
+            group_sync<NT>();
             const int8_t *mh = job.trh == TX_DCT2 ? nullptr : dxt_matrix(job.trh, w);
             for (int g = tid; g < (n >> 2); g += NT) {
                 const int x = g & (w - 1), y0 = (g >> job.log2_w) << 2;
@@ -422,7 +418,7 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
                 }
                 tmp[o] = v;
             }
-            ITX_SYNC();
+            group_sync<NT>();
             // row pass (horizontal type, size w) with nz = nzw
             const int cnt2 = inputs_used(job.trh, w, nzw);
             for (int o = tid; o < n; o += NT) {
@@ -434,7 +430,7 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
         sh_final = 6 + range - bd;
         if (dc_only) {
             const int dc = (buf[0] * 64 + (1 << (sh_final - 1))) >> sh_final;
-            ITX_SYNC();
+            group_sync<NT>();
             for (int i = tid; i < n; i += NT)
                 buf[i] = dc;
             sh_final = -1;
@@ -443,12 +439,12 @@ __device__ __forceinline__ void itx_generic_block(const vvc355_itx_job &job, int
             const int cnt = inputs_used(type, n, nz);
             for (int o = tid; o < n; o += NT)
                 tmp[o] = inv_tx_out(type, n, o, buf, 1, cnt, cos_lds);
-            ITX_SYNC();
+            group_sync<NT>();
             for (int o = tid; o < n; o += NT)
                 buf[o] = tmp[o];
         }
     }
-    ITX_SYNC();
+    group_sync<NT>();
     // final scale, then store residuals in place (slot semantics) and/or add them to the prediction
     if (e0 < n) {
         int r[PER];
@@ -541,13 +537,6 @@ __global__ __launch_bounds__(256) void itx_kernel(const vvc355_itx_job *__restri
 //   tab[type][out][k]  the transform matrices of this shape (generated: itx16_<N> in tables.inc)
 // Only the coefficients inside the nz window are fetched from HBM.  A workgroup in which any block is not eligible
 // (other shape, range > 15, a coefficient beyond 16 bits) redoes all of its blocks with the generic code above.
-
-typedef short itx_v2s __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int dot2_i16(uint32_t a, uint32_t b, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(itx_v2s, a), __builtin_bit_cast(itx_v2s, b), acc, false);
-}
-__device__ __forceinline__ uint32_t pack_i16(int lo, int hi) { return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16); }
 
 template <int N> struct TxDim {
     static constexpr int KV = N < 32 ? N : 32;               // inputs an N-point inverse transform can read
@@ -745,8 +734,7 @@ __global__ __launch_bounds__(256) void lfnst_batch_kernel(const vvc355_lfnst_job
                 gst<int>(coeffs + (y << lw) + x, dq.apply(c, x, y));
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the gather below reads what other lanes of this wave stored
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_sync();
     }
     const bool big = w >= 8 && h >= 8;
     const int n_out = big ? 48 : 16;
@@ -755,8 +743,7 @@ __global__ __launch_bounds__(256) void lfnst_batch_kernel(const vvc355_lfnst_job
     const unsigned long long sx = kDiag4X, sy = kDiag4Y;
     if (lane < 16)
         u_all[wave][lane] = lane < nz ? gld<int>(coeffs + w * (int)((sy >> (4 * lane)) & 15) + (int)((sx >> (4 * lane)) & 15)) : 0;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_sync();
     if (lane < n_out) {
         const int mode = job.pred_mode_intra;
         const int set = mode < 0 ? 1 : d_tab_lfnst_tr_set_index[mode];
@@ -1147,7 +1134,6 @@ __global__ __launch_bounds__(256) void inter_tb_shape_kernel(const vvc355_inter_
 #include "itx_shape_body.inc"
 #undef ITX_SHAPE_RECORDS
 }
-#undef ITX_SYNC
 
 // bin 25, blocks with a side of 1 or 2 (at most 128 coefficients): a wave per block through the generic code
 template <int BD>

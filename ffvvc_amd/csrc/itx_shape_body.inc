@@ -154,9 +154,9 @@
     if (y0 < KVV && x0 < KVH) {
 #pragma unroll
         for (int q = 0; q < 4; q++)
-            *(uint2 *)&cT[(x0 + q) * PV + y0] = make_uint2(pack_i16(c[0][q], c[1][q]), pack_i16(c[2][q], c[3][q]));
+            *(uint2 *)&cT[(x0 + q) * PV + y0] = make_uint2(pack16(c[0][q], c[1][q]), pack16(c[2][q], c[3][q]));
     }
-    ITX_SYNC();
+    group_sync<NT>();
 
     // ---- column pass: tile (rows ya.., columns xa..) of tmp, only the columns the row pass reads
     {
@@ -182,7 +182,7 @@
 #pragma unroll
                         for (int q = 0; q < 4; q++)
 #pragma unroll
-                            for (int e = 0; e < KSV / 2; e++) acc[r][q] = dot2_i16(m[r][e], d[q][e], acc[r][q]);
+                            for (int e = 0; e < KSV / 2; e++) acc[r][q] = dot2(m[r][e], d[q][e], acc[r][q]);
                 }
             }
 #pragma unroll
@@ -190,11 +190,11 @@
                 int v[4];
 #pragma unroll
                 for (int q = 0; q < 4; q++) v[q] = clip_intp2((acc[r][q] + 64) >> 7, range);
-                *(uint2 *)&tmp[(ya + r) * PH + xa] = make_uint2(pack_i16(v[0], v[1]), pack_i16(v[2], v[3]));
+                *(uint2 *)&tmp[(ya + r) * PH + xa] = make_uint2(pack16(v[0], v[1]), pack16(v[2], v[3]));
             }
         }
     }
-    ITX_SYNC();
+    group_sync<NT>();
 
     // ---- row pass on this lane's I/O tile
     int acc[4][4];
@@ -216,7 +216,7 @@
 #pragma unroll
                 for (int q = 0; q < 4; q++)
 #pragma unroll
-                    for (int e = 0; e < KSH / 2; e++) acc[r][q] = dot2_i16(m[q][e], d[r][e], acc[r][q]);
+                    for (int e = 0; e < KSH / 2; e++) acc[r][q] = dot2(m[q][e], d[r][e], acc[r][q]);
         }
     }
     if (!valid)

@@ -5,6 +5,7 @@
 // libavcodec/h26x/h2656_sao_template.c:24-215, libavcodec/h26x/h2656_deblock_template.c:25-99, and for the batched SAO
 // stage the caller's border rules libavcodec/vvc/vvc_filter.c:154-300.
 #include "common.hpp"
+#include "pk16.hpp"
 #include "runtime.hpp"
 #include "bs_rules.hpp"
 #include "../../include/vvc_mi355.h"
@@ -189,42 +190,13 @@ __global__ __launch_bounds__(256) void sao_kernel(const vvc355_sao_job *__restri
     }
 }
 
-// ---- packed 16-bit helpers of the vectorised SAO: a register holds two samples
-typedef short pk16 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ pk16 pk(uint32_t v) { return __builtin_bit_cast(pk16, v); }
-__device__ __forceinline__ uint32_t un(pk16 v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ pk16 pk_splat(int v) { return pk16{ (short)v, (short)v }; }
-// the compiler lowers min / max against small constants to compare + select per half: pin the packed instructions
-__device__ __forceinline__ pk16 pk_min(pk16 a, pk16 b)
-{
-    pk16 r;
-    asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ pk16 pk_max(pk16 a, pk16 b)
-{
-    pk16 r;
-    asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-template <int BD> __device__ __forceinline__ void load8_pk(const typename Px<BD>::type *p, uint32_t (&d)[4])
-{
-    if (BD > 8) {
-        const uint4 q = gld<uint4>(p);
-        d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
-    } else {
-        const uint2 q = gld<uint2>(p);
-        d[0] = __builtin_amdgcn_perm(0, q.x, 0x0c010c00u); d[1] = __builtin_amdgcn_perm(0, q.x, 0x0c030c02u);
-        d[2] = __builtin_amdgcn_perm(0, q.y, 0x0c010c00u); d[3] = __builtin_amdgcn_perm(0, q.y, 0x0c030c02u);
-    }
-}
+// ---- the vectorised SAO works on packed 16-bit samples (pk16.hpp): a register holds two of them
 template <int BD> __device__ __forceinline__ void store8_pk(typename Px<BD>::type *p, const uint32_t (&d)[4])
 {
     if (BD > 8)
         gst<uint4>(p, make_uint4(d[0], d[1], d[2], d[3]));
     else
-        gst<uint2>(p, make_uint2(__builtin_amdgcn_perm(d[1], d[0], 0x06040200u), __builtin_amdgcn_perm(d[3], d[2], 0x06040200u)));
+        gst<uint2>(p, make_uint2(narrow4(d[0], d[1]), narrow4(d[2], d[3])));
 }
 
 // the aligned vector t displaced by DX samples; e = the one sample beyond its end on that side
@@ -258,13 +230,13 @@ __device__ __forceinline__ void sao_edge8(const uint32_t (&c)[4], const uint32_t
     const pk16 one = pk_splat(1), mone = pk_splat(-1), two = pk_splat(2), zero = pk_splat(0), top = pk_splat((1 << BD) - 1);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        const pk16 s1 = pk_max(pk_min(pk(c[i]) - pk(a[i]), one), mone);
-        const pk16 s2 = pk_max(pk_min(pk(c[i]) - pk(b[i]), one), mone);
+        const pk16 s1 = pk_max_pinned(pk_min_pinned(pk(c[i]) - pk(a[i]), one), mone);
+        const pk16 s2 = pk_max_pinned(pk_min_pinned(pk(c[i]) - pk(b[i]), one), mone);
         const uint32_t idx = un(s1 + s2 + two);                              // 0..4 in the low byte of each half
         const uint32_t off = __builtin_amdgcn_perm(lut.lo_b, lut.lo_a, idx | 0x0c000c00u)
                            | __builtin_amdgcn_perm(lut.hi_b, lut.hi_a, (idx << 8) | 0x000c000cu);
         const pk16 v = __builtin_elementwise_add_sat(pk(c[i]), pk(off));     // saturating: exact for any 16-bit offset
-        out[i] = un(pk_min(pk_max(v, zero), top));
+        out[i] = un(pk_min_pinned(pk_max_pinned(v, zero), top));
     }
 }
 
@@ -339,10 +311,10 @@ __device__ __forceinline__ void sao_vec_body(const vvc355_sao_job &job, int bx, 
             for (int i = 0; i < 4; i++) {
                 uint32_t band;
                 asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(band) : "v"(sh), "v"(v[r + 1][i]));
-                const uint32_t idx = un(pk_min(pk(un(pk(band) - pos) & 0x001f001fu), four));
+                const uint32_t idx = un(pk_min_pinned(pk(un(pk(band) - pos) & 0x001f001fu), four));
                 const uint32_t off = __builtin_amdgcn_perm(0u, lo_a, idx | 0x0c000c00u) | __builtin_amdgcn_perm(0u, hi_a, (idx << 8) | 0x000c000cu);
                 const pk16 t = __builtin_elementwise_add_sat(pk(v[r + 1][i]), pk(off));
-                out[r][i] = un(pk_min(pk_max(t, zero), top));
+                out[r][i] = un(pk_min_pinned(pk_max_pinned(t, zero), top));
             }
     } else {
         // category -> offset as two byte look-ups (v_perm_b32): low bytes and high bytes of offset_val[kSaoCat[0..4]]
@@ -823,8 +795,8 @@ __global__ __launch_bounds__(256) void deblock_kernel(const vvc355_deblock_job *
                                gld<uint8_t>(&jp->max_len_q[seg]));
 }
 
-// ---- packed 16-bit form of a segment, for the picture pass at BD <= 10.  A register holds one tap of TWO lines (the SAO helpers
-// above: pk16, pk_min / pk_max), so a tap of the 4-line segment is a register pair: [0] = lines (0, 1), [1] = lines (2, 3), the even
+// ---- packed 16-bit form of a segment, for the picture pass at BD <= 10.  A register holds one tap of TWO lines (pk16.hpp,
+// with the pinned min / max as in the SAO above), so a tap of the 4-line segment is a register pair: [0] = lines (0, 1), [1] = lines (2, 3), the even
 // line in the low half.  That is what the horizontal pass loads (the four lines of a tap row are consecutive in memory: one 8-byte
 // load at 10 bits, one v_perm per register to widen 8-bit samples); the vertical pass loads four taps of a line and pairs the
 // lines with one v_perm per register.  The decisions read lines 0 and 3 (0 and 1 of a 2-line chroma segment): one more v_perm per
@@ -837,18 +809,7 @@ __global__ __launch_bounds__(256) void deblock_kernel(const vvc355_deblock_job *
 //   weak delta before the shift: |9 * (q0 - p0) - 3 * (q1 - p1) + 8| <= 12 * 1023 + 8 = 12284; 10 * tc <= 3950; 3 * tc <= 1185
 //   long filter: m * wt + ref * (64 - wt) + 32 <= 1023 * 64 + 32 = 65504: UNSIGNED 16-bit multiply-add and logical shift, only the
 //   difference to the old tap after it is signed (|.| <= 1023)
-typedef unsigned short upk16 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ upk16 upk(pk16 v) { return __builtin_bit_cast(upk16, v); }
-__device__ __forceinline__ upk16 upk_splat(int v) { return upk16{ (unsigned short)v, (unsigned short)v }; }
-__device__ __forceinline__ pk16 pk_abs(pk16 v) { return pk_max(v, pk_splat(0) - v); }
-__device__ __forceinline__ pk16 pk_clip(pk16 v, pk16 lo, pk16 hi) { return pk_max(pk_min(v, hi), lo); }
-__device__ __forceinline__ pk16 pk_clip_sym(pk16 v, int lim) { return pk_clip(v, pk_splat(-lim), pk_splat(lim)); }
-__device__ __forceinline__ pk16 pk_sel(bool c, pk16 a, pk16 b) { return pk(c ? un(a) : un(b)); }
-__device__ __forceinline__ pk16 pk_d2(pk16 a, pk16 b, pk16 c) { return pk_abs(a - b - b + c); }
-__device__ __forceinline__ pk16 pk_sar(pk16 v, int n) { return v >> pk_splat(n); }
 __device__ __forceinline__ uint32_t opaque(uint32_t v) { asm("" : "+v"(v)); return v; }
-__device__ __forceinline__ int pk_lo(pk16 v) { return v.x; }
-__device__ __forceinline__ int pk_hi(pk16 v) { return v.y; }
 
 template <int BD> struct DbkPk {
     using px_t = typename Px<BD>::type;
@@ -860,7 +821,7 @@ template <int BD> struct DbkPk {
     // lines (0, 3) of a tap — (0, 1) of a 2-line segment — in one register
     __device__ __forceinline__ pk16 dec(const uint32_t (&r)[2]) const
     {
-        return pk(lines == 2 ? r[0] : __builtin_amdgcn_perm(r[1], r[0], 0x07060100u));
+        return pk(lines == 2 ? r[0] : lo_hi(r[0], r[1]));
     }
     __device__ __forceinline__ void row(int o, uint32_t (&r)[2]) const
     {
@@ -870,7 +831,7 @@ template <int BD> struct DbkPk {
             else { r[0] = gld<uint32_t>(a); r[1] = 0; }
         } else {
             const uint32_t v = lines == 4 ? gld<uint32_t>(a) : (uint32_t)gld<uint16_t>(a);
-            r[0] = __builtin_amdgcn_perm(0, v, 0x0c010c00u); r[1] = __builtin_amdgcn_perm(0, v, 0x0c030c02u);
+            r[0] = widen_lo(v); r[1] = widen_hi(v);
         }
     }
     // taps [4 * half, 4 * half + 4) of the sides in `which` (1: p, 2: q, 3: both); the others are left as they are
@@ -896,7 +857,7 @@ template <int BD> struct DbkPk {
                 for (int k = 0; k < 4; k++)
 #pragma unroll
                     for (int j = 0; j < 2; j++) {
-                        const uint32_t t = BD > 8 ? __builtin_amdgcn_perm(L[2 * j + 1][k >> 1], L[2 * j][k >> 1], (k & 1) ? 0x07060302u : 0x05040100u)
+                        const uint32_t t = BD > 8 ? pk_half_pair(L[2 * j][k >> 1], L[2 * j + 1][k >> 1], k & 1)
                                                   : __builtin_amdgcn_perm(L[2 * j + 1][0], L[2 * j][0], 0x0c040c00u + k * 0x00010001u);
                         if (s) Q[b + k][j] = t; else P[b + 3 - k][j] = t;
                     }
@@ -915,7 +876,7 @@ template <int BD> struct DbkPk {
         if (BD > 8) {
             if (lines == 4) gst<uint2>(a, make_uint2(r[0], r[1])); else gst<uint32_t>(a, r[0]);
         } else {
-            const uint32_t v = __builtin_amdgcn_perm(r[1], r[0], 0x06040200u);
+            const uint32_t v = narrow4(r[0], r[1]);
             if (lines == 4) gst<uint32_t>(a, v); else gst<uint16_t>(a, (uint16_t)v);
         }
     }
@@ -923,7 +884,7 @@ template <int BD> struct DbkPk {
     __device__ __forceinline__ void put_pair(int o, uint32_t first, uint32_t second, int h) const
     {
         px_t *a = (px_t *)pix + o;
-        if (BD > 8) gst<uint32_t>(a, __builtin_amdgcn_perm(second, first, h ? 0x07060302u : 0x05040100u));
+        if (BD > 8) gst<uint32_t>(a, pk_half_pair(first, second, h));
         else gst<uint16_t>(a, (uint16_t)__builtin_amdgcn_perm(second, first, h ? 0x0c0c0602u : 0x0c0c0400u));
     }
     // Write back taps [0, np) of the p side and [0, nq) of the q side.  Horizontal pass: a tap row is one store (8 bytes at 10

@@ -1,5 +1,5 @@
 // Chroma bi-prediction of FOUR Cb/Cr pairs per wave for gfx950: the 4:2:0 8x8 blocks of four consecutive sub-blocks, one pair per
-// 16-lane group.  Included by mc_fused.hip (inside namespace vvc355); the one-pair path there stays the path of everything else.
+// 16-lane group.  Used by mc_fused.hip's chroma bi-prediction kernel; the one-pair path there stays the path of everything else.
 //
 // The stage is bound by VALU issue, and what the one-pair path issues is mostly overhead paid per wave for 128 samples: clamped
 // 2-byte loads, partly filled passes, a descriptor unpacked on the scalar unit.  Here a wave produces 512 samples:
@@ -20,6 +20,13 @@
 //    references, 8 rows.  v_dot2 on aligned pairs; the parity of d is folded into the tap registers (two sets of three).
 //  * Epilogue: avg is w_avg with weights 1, denom 0 and offsets 0, so one formula per lane with its plane's weights.
 #pragma once
+#include "common.hpp"
+#include "pk16.hpp"
+#include "wave.hpp"
+#include "mc_filters.hpp"
+#include "../../include/vvc_mi355.h"
+
+namespace vvc355 {
 
 static constexpr int kQwP = 20;         // window pitch in samples: 2 pad + window columns 0..10 at LDS columns 4..14 + 5 pad (8-byte rows)
 static constexpr int kQwC0 = 4;         // LDS column of window column 0
@@ -135,7 +142,7 @@ __device__ __forceinline__ bool chroma_quad(const vvc355_bipred_job *jobs, int i
                 v[r] = gld<uint2>(p);
             } else {
                 const uint32_t s = gld<uint32_t>(p);
-                v[r] = make_uint2(__builtin_amdgcn_perm(0, s, 0x0c010c00u), __builtin_amdgcn_perm(0, s, 0x0c030c02u));
+                v[r] = make_uint2(widen_lo(s), widen_hi(s));
             }
             p += stride;
         }
@@ -143,12 +150,12 @@ __device__ __forceinline__ bool chroma_quad(const vvc355_bipred_job *jobs, int i
 #pragma unroll
         for (int r = 0; r < kQwRows; r++) {
             uint2 d = v[r];
-            const uint32_t rep = __builtin_amdgcn_perm(0, d.y, 0x01000100u);         // window column 10 twice
+            const uint32_t rep = pk_dup_lo(d.y);                                     // window column 10 twice
             if (k >= 2) d.y = rep;                                                   // column 11 is past the window
             if (k == 3) d.x = rep;
             *(uint2 *)(wq + r * kQwP) = d;
             if (k == 0)
-                *(uint32_t *)(wq + r * kQwP - 2) = __builtin_amdgcn_perm(0, d.x, 0x01000100u);       // left pad: column 0 twice
+                *(uint32_t *)(wq + r * kQwP - 2) = pk_dup_lo(d.x);                   // left pad: column 0 twice
         }
         wave_sync();
     }
@@ -216,3 +223,5 @@ __device__ __forceinline__ bool chroma_quad(const vvc355_bipred_job *jobs, int i
     }
     return true;
 }
+
+} // namespace vvc355

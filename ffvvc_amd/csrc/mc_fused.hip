@@ -15,60 +15,19 @@
 // pairs.  The kernel is VALU-issue bound (rocprofv3: > 80 % of the per-SIMD VALU slots), hence the 4-tap specialisation.
 #include <type_traits>
 #include "common.hpp"
+#include "pk16.hpp"
+#include "wave.hpp"
+#include "mc_filters.hpp"
+#include "mc_tools.hpp"
+#include "mc_chroma_quad.hpp"
 #include "runtime.hpp"
 #include "../../include/vvc_mi355.h"
 
 namespace vvc355 {
 
-#define VVC355_TABLE(type, name, count) __device__ static const type d_tab_##name[count]
-#include "tables.inc"
-#undef VVC355_TABLE
-
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int dot2(uint32_t a, uint32_t b, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, a), __builtin_bit_cast(v2s, b), acc, false);
-}
-__device__ __forceinline__ uint32_t pack16(int lo, int hi) { return (uint32_t)(lo & 0xffff) | ((uint32_t)hi << 16); }
-__device__ __forceinline__ int tap_of(uint32_t lo, uint32_t hi, int k)      // signed byte k of the 8-byte tap vector
-{
-    const uint32_t v = k < 4 ? lo : hi;
-    return (int)(int8_t)(v >> ((k & 3) * 8));
-}
-
 static constexpr int kWinW = 24;      // LDS source window: up to 16 + 8 columns, even pitch
 static constexpr int kWinH = 23;
 static constexpr int kTmpP = 24;      // transposed intermediate: [column][row], up to 23 rows (+1 read-only slack), even pitch
-
-// Two adjacent outputs of an NTAP-tap filter from aligned sample pairs d[m] = (p[2m], p[2m+1]):
-// out0 = sum f[k] p[k], out1 = sum f[k] p[k+1].
-template <int NTAP> struct Taps {
-    static constexpr int NE = NTAP / 2, NO = NTAP / 2 + 1;
-    uint32_t e[NE];     // (f0,f1) (f2,f3) ...
-    uint32_t o[NO];     // (0,f0) (f1,f2) ... (f_last,0)
-    __device__ __forceinline__ void set(uint32_t lo, uint32_t hi)
-    {
-        int f[NTAP];
-#pragma unroll
-        for (int k = 0; k < NTAP; k++) f[k] = tap_of(lo, hi, k);
-#pragma unroll
-        for (int m = 0; m < NE; m++) e[m] = pack16(f[2 * m], f[2 * m + 1]);
-        o[0] = pack16(0, f[0]);
-#pragma unroll
-        for (int m = 1; m < NE; m++) o[m] = pack16(f[2 * m - 1], f[2 * m]);
-        o[NE] = pack16(f[NTAP - 1], 0);
-    }
-    __device__ __forceinline__ void apply(const uint32_t (&d)[NO], int &out0, int &out1) const
-    {
-        int a = 0, b = 0;
-#pragma unroll
-        for (int m = 0; m < NE; m++) a = dot2(d[m], e[m], a);
-#pragma unroll
-        for (int m = 0; m < NO; m++) b = dot2(d[m], o[m], b);
-        out0 = a; out1 = b;
-    }
-};
 
 // Window staging is split in two so that the loads of BOTH references are in flight before anything waits on them.
 // Window index (r, c) <-> picture sample (r - LEAD, c - LEAD) when that direction is filtered, else (r, c - LEAD):
@@ -149,8 +108,7 @@ __device__ __forceinline__ void interp_block(int lw, int h, bool hfrac, bool vfr
             tmpT[x * kTmpP + r] = (int16_t)win[r * kWinW + x + LEAD + (SPLIT && x >= 8 ? 4 : 0)];           // raw samples
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_sync();
 
     // ---- vertical pass: lane -> column x, two row pairs
     const int x = lane & 15;
@@ -180,8 +138,7 @@ __device__ __forceinline__ void interp_block(int lw, int h, bool hfrac, bool vfr
         val[2 * i] = o0;
         val[2 * i + 1] = o1;
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_sync();
 }
 
 // both references of one block: windows requested together, then interpolated one after the other
@@ -198,8 +155,7 @@ __device__ __forceinline__ void predict_refs(const vvc355_pred_job *job, int lw,
         store_window<NTAP>(win[0], lane, r0);
         if (mode < 2)
             store_window<NTAP>(win[1], lane, r1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_sync();
     }
     interp_block<BD, NTAP>(lw, h, frac & 1, frac & 2, taps[0], taps[1], taps[2], taps[3], win[0], tmpT, lane, v0);
     if (mode < 2)
@@ -305,7 +261,7 @@ __device__ __forceinline__ void fetch_vec4(const uint8_t *plane, int stride, int
             v[it] = gld_at<uint2>(org, p);
         } else {
             const uint32_t q = gld_at<uint32_t>(org, p);
-            v[it] = make_uint2(__builtin_amdgcn_perm(0, q, 0x0c010c00u), __builtin_amdgcn_perm(0, q, 0x0c030c02u));
+            v[it] = make_uint2(widen_lo(q), widen_hi(q));
         }
     }
 }
@@ -322,12 +278,6 @@ __device__ __forceinline__ void put_vec4(uint16_t *win, int nrows, int lane, con
 __device__ __forceinline__ bool rect_holds(const ClampRect &rc, int wx0, int wy0, int nrows)
 {
     return wx0 >= rc.x0 && wx0 + kWinW - 1 <= rc.x1 && wy0 >= rc.y0 && wy0 + nrows - 1 <= rc.y1;
-}
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
 }
 
 // Per-wave LDS of the plain path (both reference windows, the transposed intermediate of interp_block): 2.9 KB per wave
@@ -418,8 +368,6 @@ __device__ __forceinline__ void predict_clamped(const vvc355_bipred_job *job, Bi
         for (int i = 0; i < 4; i++) v1[i] = 0;
     }
 }
-
-#include "mc_tools.hpp"
 
 // what one wave of a luma launch needs: the plain path's planes or the tools path's (5.6 KB: 28 waves per CU)
 union BipredLdsAll {
@@ -552,8 +500,6 @@ __global__ __launch_bounds__(256) void gpm_kernel(const vvc355_gpm_job *__restri
     base.pred_flag = 3; base.dmvr = 0; base.bdof = 0; base.weight_flag = 0; base.rec = 0;
     bipred_plain<BD>(&base, lds_all[wave], lane, &job);
 }
-
-#include "mc_chroma_quad.hpp"
 
 // One PAIR of consecutive jobs, ia and ia + 1, by one wave.  When the two are the Cb and Cr blocks of one sub-block (same
 // geometry and motion, width <= 8) they are predicted together as one 16-wide block whose halves come from two planes —

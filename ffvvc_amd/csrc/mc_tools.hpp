@@ -1,6 +1,6 @@
 // Regular bi-prediction with the decoder-side tools (DMVR and / or BDOF) for gfx950 — the shapes those tools run on:
 // sub-blocks of 8 or 16 samples on a side (vvc_inter.c:772-822, pred_regular_blk: derive_sb_mv -> dmvr_mv_refine :685-748,
-// luma_mc_bi :253-296, apply_bdof vvc_inter_template.c:288).  Included by mc_fused.hip (inside namespace vvc355).
+// luma_mc_bi :253-296, apply_bdof vvc_inter_template.c:288).  Used by mc_fused.hip's luma bi-prediction kernel.
 //
 // One wave per sub-block, W and H compile-time, every loop unrolled.  What bounds this stage is VALU issue, not HBM, so the
 // design goal is instruction count:
@@ -21,20 +21,14 @@
 //    DPP adds inside the 16-lane row; ring replication = doubled edge weights (columns) / own-row reads (rows);
 //    the output is one v_dot2 per sample on (ghd, gvd) x (vx, vy).
 #pragma once
+#include <type_traits>
+#include "common.hpp"
+#include "pk16.hpp"
+#include "wave.hpp"
+#include "mc_filters.hpp"
+#include "../../include/vvc_mi355.h"
 
-typedef short pk_i16 __attribute__((ext_vector_type(2)));
-typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ pk_i16 as_pk(uint32_t v) { return __builtin_bit_cast(pk_i16, v); }
-__device__ __forceinline__ uint32_t as_u32(pk_i16 v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ pk_i16 pk_splat(int v) { return pk_i16{ (short)v, (short)v }; }
-__device__ __forceinline__ pk_i16 pk_max(pk_i16 a, pk_i16 b) { return __builtin_elementwise_max(a, b); }
-__device__ __forceinline__ pk_i16 pk_min(pk_i16 a, pk_i16 b) { return __builtin_elementwise_min(a, b); }
-
-// DPP move with zero fill: lane <- the lane CTRL selects, 0 when that lane does not exist
-template <int CTRL> __device__ __forceinline__ int dpp0(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-static constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141;          // quad_perm [1,0,3,2], [2,3,0,1]
-static constexpr int kDppShr1 = 0x111, kDppShr2 = 0x112, kDppShl1 = 0x101, kDppQuad2 = 0xAA;   // quad_perm [2,2,2,2]
+namespace vvc355 {
 
 static constexpr int kTwP = 40;         // window pitch in samples: 20 dwords, so 4 consecutive row pairs x 8 dwords tile the 32 banks
 static constexpr int kTwC0 = 5;         // LDS column of window column 0 (3 pad columns + alignment: window column 1 sits on an even column)
@@ -53,22 +47,6 @@ template <int W, int H> struct ToolsLds {
 };
 // the vertical exchange of the BDOF box sums overlays the (by then dead) windows: [quantity][column][by][pair]
 static constexpr int kXchBytes = 5 * 16 * 4 * 2 * 4;
-
-struct Taps8 { uint32_t e[4], o[5]; };
-__device__ __forceinline__ Taps8 make_taps8(uint32_t lo, uint32_t hi)
-{
-    int f[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) f[k] = tap_of(lo, hi, k);
-    Taps8 t;
-#pragma unroll
-    for (int m = 0; m < 4; m++) t.e[m] = pack16(f[2 * m], f[2 * m + 1]);
-    t.o[0] = pack16(0, f[0]);
-#pragma unroll
-    for (int m = 1; m < 4; m++) t.o[m] = pack16(f[2 * m - 1], f[2 * m]);
-    t.o[4] = pack16(f[7], 0);
-    return t;
-}
 
 // vvc_inter.c:642-681
 __device__ __forceinline__ int parametric_mv_refine(int sad_minus, int sad_center, int sad_plus)
@@ -141,7 +119,7 @@ __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, Tools
                 for (int it = 0; it < NIT; it++) {
                     uint2 v;
                     if constexpr (BD > 8) v = q[i][it];
-                    else v = make_uint2(__builtin_amdgcn_perm(0, q[i][it], 0x0c010c00u), __builtin_amdgcn_perm(0, q[i][it], 0x0c030c02u));
+                    else v = make_uint2(widen_lo(q[i][it]), widen_hi(q[i][it]));
                     *(uint2 *)&L.win[i][(rsub + 8 * it) * kTwP + 4 + 4 * k] = v;             // column -1 lands on LDS column 4
                 }
         }
@@ -200,20 +178,19 @@ __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, Tools
                 if constexpr (BD <= 10) {
                     // up to 10 bits the four variants are one formula (a zero fraction gives 16 x sample, (16 s + off1) >> sh1 =
                     // s << (10 - bd), (16 t + 8) >> 4 = t), and every intermediate fits 16 bits: packed arithmetic on the pair
-                    auto PK = [](uint32_t v) { return __builtin_bit_cast(pk_u16, v); };
-                    auto SP = [](int v) { return pk_u16{ (unsigned short)v, (unsigned short)v }; };
-                    const pk_u16 MX = SP(mx), MX16 = SP(16 - mx), MY = SP(my), MY16 = SP(16 - my), OFF1 = SP(off1), EIGHT = SP(8);
-                    auto hstage = [&](int r) -> pk_u16 {
+                    const upk16 MX = upk_splat(mx), MX16 = upk_splat(16 - mx), MY = upk_splat(my), MY16 = upk_splat(16 - my);
+                    const upk16 OFF1 = upk_splat(off1), EIGHT = upk_splat(8);
+                    auto hstage = [&](int r) -> upk16 {
                         const uint32_t p0 = *(const uint32_t *)(win + r * kTwP), p1 = *(const uint32_t *)(win + r * kTwP + 2);
-                        return (PK(p0) * MX16 + PK(__builtin_amdgcn_alignbit(p1, p0, 16)) * MX + OFF1) >> SP(sh1);
+                        return (upk(pk(p0)) * MX16 + upk(pk(__builtin_amdgcn_alignbit(p1, p0, 16))) * MX + OFF1) >> upk_splat(sh1);
                     };
-                    pk_u16 a = hstage(r0);
+                    upk16 a = hstage(r0);
 #pragma unroll
                     for (int rr = 0; rr < RPS; rr++) {
                         const int r = r0 + rr;
                         if (r < PH) {
-                            const pk_u16 b = hstage(r + 1);
-                            const pk_u16 v = (a * MY16 + b * MY + EIGHT) >> SP(4);
+                            const upk16 b = hstage(r + 1);
+                            const upk16 v = (a * MY16 + b * MY + EIGHT) >> upk_splat(4);
                             *(uint32_t *)&out[r * PW] = __builtin_bit_cast(uint32_t, v);
                             a = b;
                         }
@@ -365,7 +342,8 @@ __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, Tools
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             const uint2 hf = load_uniform((const uint2 *)(d_tab_inter_luma_filters + (job->hf_idx * 16 + fxr[i]) * 8));
-            const Taps8 t = make_taps8(hf.x, hf.y);
+            Taps<8> t;
+            t.set(hf.x, hf.y);
             const bool odd = dxr[i] & 1;
 #pragma unroll
             for (int m = 0; m < 5; m++) {
@@ -416,7 +394,8 @@ __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, Tools
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const uint2 vf = load_uniform((const uint2 *)(d_tab_inter_luma_filters + (job->vf_idx * 16 + fyr[i]) * 8));
-        const Taps8 t = make_taps8(vf.x, vf.y);
+        Taps<8> t;
+        t.set(vf.x, vf.y);
         const uint2 *p = (const uint2 *)(L.tmpT[i] + x * kTtP + 4 * by);
         uint32_t d[6];
 #pragma unroll
@@ -483,35 +462,35 @@ __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, Tools
     }
     wave_sync();
     // gradients on packed row pairs (prof_grad_filter :135): gh = (right >> 6) - (left >> 6), gv = (below >> 6) - (above >> 6)
-    const pk_i16 S6 = pk_splat(6);
-    pk_i16 gh[2][2], gvp[2][2];
+    const pk16 S6 = pk_splat(6);
+    pk16 gh[2][2], gvp[2][2];
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const uint32_t *cl = (const uint32_t *)(L.smp[i] + x * kSmP + 4 * by);              // column x - 1
         const uint32_t *cc = (const uint32_t *)(L.smp[i] + (x + 1) * kSmP + 4 * by);
         const uint32_t *cr = (const uint32_t *)(L.smp[i] + (x + 2) * kSmP + 4 * by);
         const uint32_t l0 = cl[1], l1 = cl[2], r0 = cr[1], r1 = cr[2], up = cc[0], dn = cc[3];
-        gh[i][0] = (as_pk(r0) >> S6) - (as_pk(l0) >> S6);
-        gh[i][1] = (as_pk(r1) >> S6) - (as_pk(l1) >> S6);
-        const pk_i16 a0 = as_pk(__builtin_amdgcn_alignbit(sp[i][0], up, 16)) >> S6;         // rows 4 by - 1, 4 by
-        const pk_i16 a1 = as_pk(__builtin_amdgcn_alignbit(sp[i][1], sp[i][0], 16)) >> S6;   // rows 4 by + 1, 4 by + 2
-        const pk_i16 a2 = as_pk(__builtin_amdgcn_alignbit(dn, sp[i][1], 16)) >> S6;         // rows 4 by + 3, 4 by + 4
+        gh[i][0] = (pk(r0) >> S6) - (pk(l0) >> S6);
+        gh[i][1] = (pk(r1) >> S6) - (pk(l1) >> S6);
+        const pk16 a0 = pk(__builtin_amdgcn_alignbit(sp[i][0], up, 16)) >> S6;         // rows 4 by - 1, 4 by
+        const pk16 a1 = pk(__builtin_amdgcn_alignbit(sp[i][1], sp[i][0], 16)) >> S6;   // rows 4 by + 1, 4 by + 2
+        const pk16 a2 = pk(__builtin_amdgcn_alignbit(dn, sp[i][1], 16)) >> S6;         // rows 4 by + 3, 4 by + 4
         gvp[i][0] = a1 - a0;
         gvp[i][1] = a2 - a1;
     }
     wave_sync();                                         // every lane has read the ring: the windows are dead, the exchange overlays them
     // per row pair: D = (s0 >> 4) - (s1 >> 4), TH = (gh0 + gh1) >> 1, TV = (gv0 + gv1) >> 1, GHD = gh0 - gh1, GVD = gv0 - gv1, then the
     // five window terms |TH|, |TV|, sign(TV) TH, -sign(TH) D, -sign(TV) D (derive_bdof_vx_vy :237)
-    const pk_i16 ONE = pk_splat(1), MONE = pk_splat(-1), ZERO = pk_splat(0), S4 = pk_splat(4);
-    pk_i16 ghd[2], gvd[2], term[5][2];
+    const pk16 ONE = pk_splat(1), MONE = pk_splat(-1), ZERO = pk_splat(0), S4 = pk_splat(4);
+    pk16 ghd[2], gvd[2], term[5][2];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-        const pk_i16 D = (as_pk(sp[0][k]) >> S4) - (as_pk(sp[1][k]) >> S4);
-        const pk_i16 th = (gh[0][k] + gh[1][k]) >> ONE, tv = (gvp[0][k] + gvp[1][k]) >> ONE;
+        const pk16 D = (pk(sp[0][k]) >> S4) - (pk(sp[1][k]) >> S4);
+        const pk16 th = (gh[0][k] + gh[1][k]) >> ONE, tv = (gvp[0][k] + gvp[1][k]) >> ONE;
         ghd[k] = gh[0][k] - gh[1][k];
         gvd[k] = gvp[0][k] - gvp[1][k];
-        const pk_i16 nth = ZERO - th, ntv = ZERO - tv;
-        const pk_i16 nsx = pk_max(pk_min(nth, ONE), MONE), nsy = pk_max(pk_min(ntv, ONE), MONE);     // -sign(th), -sign(tv)
+        const pk16 nth = ZERO - th, ntv = ZERO - tv;
+        const pk16 nsx = pk_max(pk_min(nth, ONE), MONE), nsy = pk_max(pk_min(ntv, ONE), MONE);     // -sign(th), -sign(tv)
         term[0][k] = pk_max(th, nth);
         term[1][k] = pk_max(tv, ntv);
         term[2][k] = (ZERO - nsy) * th;
@@ -527,7 +506,7 @@ __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, Tools
     if (live) {
 #pragma unroll
         for (int q = 0; q < 5; q++)
-            *(uint2 *)&xch[((q * 16 + x) * 4 + by) * 2] = make_uint2(as_u32(term[q][0]), as_u32(term[q][1]));
+            *(uint2 *)&xch[((q * 16 + x) * 4 + by) * 2] = make_uint2(un(term[q][0]), un(term[q][1]));
     }
     wave_sync();
     int tot[5];
@@ -537,7 +516,7 @@ __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, Tools
         const uint32_t su = top ? 0x00000001u : 0x00010000u, sd = bot ? 0x00010000u : 0x00000001u;
 #pragma unroll
         for (int q = 0; q < 5; q++) {
-            const uint32_t own = as_u32(term[q][0] + term[q][1]);
+            const uint32_t own = un(term[q][0] + term[q][1]);
             int t = dot2(own, 0x00010001u, 0);
             t = dot2(pu[q * 128], su, t);
             t = dot2(pd[q * 128], sd, t);
@@ -572,11 +551,13 @@ __device__ __forceinline__ void bipred_tools(const vvc355_bipred_job *job, Tools
         constexpr int sh = 15 - BD, off = 1 << (sh - 1);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const uint32_t hd = as_u32(ghd[j >> 1]), vd = as_u32(gvd[j >> 1]);
-            const uint32_t g = (j & 1) ? __builtin_amdgcn_perm(vd, hd, 0x07060302u) : __builtin_amdgcn_perm(vd, hd, 0x05040100u);
+            const uint32_t hd = un(ghd[j >> 1]), vd = un(gvd[j >> 1]);
+            const uint32_t g = (j & 1) ? pk_hh(hd, vd) : pk_ll(hd, vd);
             const int p = dot2(g, vxy, v[0][j] + v[1][j] + off) >> sh;
             gst_at<px_t>(dst, doff, (px_t)lmcs_fwd<BD>(lut, clip_px<BD>(p)));
             doff += dst_stride;
         }
     }
 }
+
+} // namespace vvc355
