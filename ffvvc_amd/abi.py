@@ -197,6 +197,15 @@ BATCH_SIGNATURES = {
     "recon_order_check": ("i", "piipi"),
     # every record-path stage of a picture in the documented order, validated as a whole before the first launch (vvc355_picture, HOST memory)
     "picture_pass":     ("i", "pip"),
+    # the recorder (include/vvc_mi355_rec.h, host only): parsed units -> RECON commands, CTU table, ticket order, the three TB record lists
+    # with their side records and level stream, arena slots; KEEP decided over the whole picture in end_picture
+    "rec_create":       ("p", ""),
+    "rec_destroy":      ("v", "p"),
+    "rec_begin_picture": ("i", "pp"),
+    "rec_ctu":          ("i", "piipi"),
+    "rec_end_picture":  ("i", "pp"),
+    "rec_fill_arena":   ("i", "pp"),
+    "rec_bind":         ("i", "pz"),
 }
 
 
@@ -909,3 +918,60 @@ class PredJob(ctypes.Structure):
         ("denom", ctypes.c_int16), ("w0", ctypes.c_int16), ("w1", ctypes.c_int16), ("o0", ctypes.c_int16), ("o1", ctypes.c_int16),
         ("pad1_", ctypes.c_int16 * 2),
     ]
+
+
+# ---- the recorder (include/vvc_mi355_rec.h): its input PODs, its result and what it returns for input it refuses
+
+class RecTb(ctypes.Structure):
+    """Mirror of vvc355_rec_tb (one transform block as the parser left it; levels = HOST int32[w * h])."""
+    _fields_ = [("levels", ctypes.c_uint64), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("w", ctypes.c_int16), ("h", ctypes.c_int16),
+                ("c_idx", ctypes.c_uint8), ("ts", ctypes.c_uint8), ("has_coeffs", ctypes.c_uint8), ("pad0_", ctypes.c_uint8),
+                ("min_x", ctypes.c_uint8), ("min_y", ctypes.c_uint8), ("max_x", ctypes.c_uint8), ("max_y", ctypes.c_uint8),
+                ("pad1_", ctypes.c_uint32)]
+
+
+class RecTu(ctypes.Structure):
+    """Mirror of vvc355_rec_tu (tbs = HOST vvc355_rec_tb[n_tbs])."""
+    _fields_ = [("tbs", ctypes.c_uint64), ("n_tbs", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32),
+                ("w", ctypes.c_int16), ("h", ctypes.c_int16), ("coded_flag", ctypes.c_uint8 * 3), ("joint_cbcr_residual_flag", ctypes.c_uint8),
+                ("pad_", ctypes.c_uint32)]
+
+
+class RecCu(ctypes.Structure):
+    """Mirror of vvc355_rec_cu (tus = HOST vvc355_rec_tu[n_tus], decoding order)."""
+    _fields_ = [("tus", ctypes.c_uint64), ("n_tus", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32),
+                ("w", ctypes.c_int16), ("h", ctypes.c_int16),
+                ("pred_mode", ctypes.c_uint8), ("tree_type", ctypes.c_uint8), ("coded_flag", ctypes.c_uint8), ("ciip_flag", ctypes.c_uint8),
+                ("mode_y", ctypes.c_int8), ("mode_c", ctypes.c_int8), ("ref_idx", ctypes.c_uint8),
+                ("mip_flag", ctypes.c_uint8), ("mip_mode", ctypes.c_uint8), ("mip_transposed", ctypes.c_uint8), ("mip_chroma_direct", ctypes.c_uint8),
+                ("isp_type", ctypes.c_uint8), ("bdpcm", ctypes.c_uint8 * 3), ("lfnst_idx", ctypes.c_uint8), ("apply_lfnst", ctypes.c_uint8 * 3),
+                ("mts_idx", ctypes.c_uint8), ("sbt_flag", ctypes.c_uint8), ("sbt_horizontal", ctypes.c_uint8), ("sbt_pos", ctypes.c_uint8),
+                ("qp", ctypes.c_int8 * 4), ("pad_", ctypes.c_uint8 * 5)]
+
+
+class RecParams(ctypes.Structure):
+    """Mirror of vvc355_rec_params."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("ctb_log2", ctypes.c_uint8), ("bit_depth", ctypes.c_uint8), ("log2_transform_range", ctypes.c_uint8), ("chroma_format_idc", ctypes.c_uint8),
+                ("qp_bd_offset", ctypes.c_int8), ("sps_min_qp_prime_ts", ctypes.c_uint8),
+                ("mts_enabled", ctypes.c_uint8), ("explicit_mts_intra", ctypes.c_uint8), ("explicit_mts_inter", ctypes.c_uint8),
+                ("ph_joint_cbcr_sign_flag", ctypes.c_uint8), ("ph_chroma_residual_scale_flag", ctypes.c_uint8), ("pack_levels", ctypes.c_uint8),
+                ("pad_", ctypes.c_uint8 * 28)]
+
+
+class RecResult(ctypes.Structure):
+    """Mirror of vvc355_rec_result: HOST addresses into the recorder's buffers, valid until its next begin_picture."""
+    _fields_ = [("cmds", ctypes.c_uint64), ("ctus", ctypes.c_uint64), ("order", ctypes.c_uint64),
+                ("intra", ctypes.c_uint64), ("inter", ctypes.c_uint64), ("ts", ctypes.c_uint64),
+                ("intra_lv", ctypes.c_uint64), ("inter_lv", ctypes.c_uint64), ("ts_lv", ctypes.c_uint64), ("levels", ctypes.c_uint64),
+                ("n_levels", ctypes.c_uint64), ("arena_len", ctypes.c_uint64),
+                ("n_cmds", ctypes.c_int32), ("n_ctus", ctypes.c_int32), ("n_work", ctypes.c_int32),
+                ("n_intra", ctypes.c_int32), ("n_inter", ctypes.c_int32), ("n_ts", ctypes.c_int32),
+                ("class_first", ctypes.c_int32 * 6), ("bin_first", (ctypes.c_int32 * (INTER_TB_BINS + 1)) * 2),
+                ("ts_first", (ctypes.c_int32 * (TS_TB_CLASSES + 1)) * 2),
+                ("keep", ctypes.c_int32), ("batched_scaled", ctypes.c_int32), ("walk_scaled", ctypes.c_int32), ("late_keep", ctypes.c_int32)]
+
+
+REC_SLICE_DEP_QUANT, REC_SLICE_LMCS = 1, 2
+(REC_E_ARGS, REC_E_STATE, REC_E_PARAMS, REC_E_CTU_RANGE, REC_E_CTU_TWICE, REC_E_CU_RECT, REC_E_TB_RECT, REC_E_SIDE, REC_E_C_IDX, REC_E_LEVELS,
+ REC_E_CIIP, REC_E_NOMEM) = range(-1, -13, -1)
