@@ -139,7 +139,10 @@ class Picture(agc.AffineGpmWork):
     """One picture of any of the three unit kinds.  agc.AffineGpmWork's expect_affine / expect_gpm / weights (the numpy walks the GPU parity
     tests use) run on it unchanged: they read width, height, hs, vs, chroma, isz, mvf, aff, gpm, slices and the job counts."""
 
-    def __init__(self, name, rng, bd, idc, ctb_log2, size, kinds, whole=None, mv_range=20 * 16, hole=0.1):
+    def __init__(self, name, rng, bd, idc, ctb_log2, size, kinds, whole=None, mv_range=20 * 16, hole=0.1, content=None, layout=None):
+        """content(self) -> refs[list][ref_idx][component], called last, replaces the smooth reference pictures; layout(self) -> (pus, aff,
+        gpm) in the forms of _regular / _affine / _gpm places the units by hand instead of the random split (it fills self.mvf, self.units
+        and self.covered, and may replace self.slices and self.ctu_slice).  Both default to None: the listed pictures draw what they drew."""
         self.name, self.bd, self.idc, self.ctb_log2, self.kinds = name, bd, idc, ctb_log2, kinds
         self.width, self.height = size
         assert self.width % 8 == 0 and self.height % 8 == 0 and self.width <= 264 and self.height <= 192
@@ -157,35 +160,41 @@ class Picture(agc.AffineGpmWork):
         self.mvf = np.zeros((H // 4, W // 4), ifc.MVF_DT)
         self.covered = np.zeros((H, W), bool)
         self.units = []                            # (kind, x, y, w, h) of every unit, for messages
-        base = [bc.smooth_picture(rng, ph, pw, bd) for (pw, ph) in self.dims]
-        self.refs = [[[bc.shifted(base[c], ref_shift(l, r)[0] >> (self.hs if c else 0), ref_shift(l, r)[1] >> (self.vs if c else 0)) for c in range(3)]
-                      for r in range(2)] for l in range(2)]
+        if content is None:
+            base = [bc.smooth_picture(rng, ph, pw, bd) for (pw, ph) in self.dims]
+            self.refs = [[[bc.shifted(base[c], ref_shift(l, r)[0] >> (self.hs if c else 0), ref_shift(l, r)[1] >> (self.vs if c else 0)) for c in range(3)]
+                          for r in range(2)] for l in range(2)]
         self.lut = np.sort(np.random.default_rng(0x10C5 + bd).integers(0, 1 << bd, size=1 << bd)).astype(px(bd))          # fc->ps.lmcs.fwd_lut
         pus, aff, gpm = [], [], []
         self._part = int(rng.integers(0, 64))
         min_side = 4 if "R" in kinds else 8
-        for rs in range(n_ctb):
-            x0, y0, sl = (rs % self.ncx) * ctb, (rs // self.ncx) * ctb, self.ctu_slice[rs]
-            leaves, forced = [], None
-            if whole and rs in whole:
-                leaves, forced = [(x0, y0, min(ctb, W - x0), min(ctb, H - y0))], whole[rs]
-            else:
-                _split(rng, x0, y0, ctb, ctb, W, H, min_side, leaves)
-            for (x, y, w, h) in leaves:
-                fits = {"R": True, "A": w >= 8 and h >= 8, "G": (w, h) in GPM_SHAPES}
-                opts = [k for k in kinds if fits[k]]
-                if not opts or (forced is None and rng.random() < hole):
-                    continue
-                kind = opts[int(rng.integers(0, len(opts)))]
-                self.covered[y:y + h, x:x + w] = True
-                self.units.append((kind, x, y, w, h))
-                if kind == "R":
-                    pus.append(self._regular(rng, x, y, w, h, sl, mv_range, forced))
-                elif kind == "A":
-                    aff.append(self._affine(rng, x, y, w, h, sl, mv_range))
+        if layout is not None:
+            pus, aff, gpm = layout(self)
+        else:
+            for rs in range(n_ctb):
+                x0, y0, sl = (rs % self.ncx) * ctb, (rs // self.ncx) * ctb, self.ctu_slice[rs]
+                leaves, forced = [], None
+                if whole and rs in whole:
+                    leaves, forced = [(x0, y0, min(ctb, W - x0), min(ctb, H - y0))], whole[rs]
                 else:
-                    gpm.append(self._gpm(rng, x, y, w, h, sl, mv_range, len(gpm)))
+                    _split(rng, x0, y0, ctb, ctb, W, H, min_side, leaves)
+                for (x, y, w, h) in leaves:
+                    fits = {"R": True, "A": w >= 8 and h >= 8, "G": (w, h) in GPM_SHAPES}
+                    opts = [k for k in kinds if fits[k]]
+                    if not opts or (forced is None and rng.random() < hole):
+                        continue
+                    kind = opts[int(rng.integers(0, len(opts)))]
+                    self.covered[y:y + h, x:x + w] = True
+                    self.units.append((kind, x, y, w, h))
+                    if kind == "R":
+                        pus.append(self._regular(rng, x, y, w, h, sl, mv_range, forced))
+                    elif kind == "A":
+                        aff.append(self._affine(rng, x, y, w, h, sl, mv_range))
+                    else:
+                        gpm.append(self._gpm(rng, x, y, w, h, sl, mv_range, len(gpm)))
         self._finish(pus, aff, gpm)
+        if content is not None:
+            self.refs = content(self)
         # the reference's PredWeightTable holds 15 entries per list: ref_idx 15 of an explicitly weighted slice would read past it
         assert int(self.mvf["ref_idx"].max()) < 15 and all(int(m["ref_idx"].max()) < 15 for cu in self.gpm for m in cu["gpm_mv"].view(ifc.MVF_DT))
 

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/ref_slots.json, tests/golden/ref_passes.json, tests/golden/ref_inter.json and tests/golden/ref_recon.json: SHA-256
+"""Regenerate tests/golden/ref_slots.json, tests/golden/ref_passes.json, tests/golden/ref_inter.json, tests/golden/ref_recon.json and
+tests/golden/ref_extremes.json (the full-scale pictures of tests/extreme_cases.py, in the format of ref_passes.json / ref_inter.json): SHA-256
 digests of what the reference's own C path computes on the case lists of tests/ref_cases.py, of what its in-loop filter callers compute on
 the pictures of tests/ref_pass_cases.py, of what its inter prediction callers compute on the pictures of tests/ref_inter_cases.py, and of what
 ff_vvc_reconstruct computes on the pictures of tests/ref_recon_cases.py.
@@ -45,6 +46,11 @@ try:                  # ... or no RECON pictures yet (ref_recon.json is then lef
     import ref_recon_cases  # noqa: E402
 except ImportError:
     ref_recon_cases = None
+
+try:                  # ... or no full-scale pictures yet (ref_extremes.json is then left alone)
+    import extreme_cases  # noqa: E402
+except ImportError:
+    extreme_cases = None
 
 CONTEXT_SLOTS_AFTER = "ilfnst_transform"          # the context slots follow vvc_intra.c's static functions in the file
 
@@ -146,6 +152,16 @@ def generate_recon(lib):
             "pictures": {name: ref_recon_cases.reference_digests(lib, name) for name in ref_recon_cases.picture_names()}}
 
 
+def generate_extremes(lib):
+    """The document of ref_extremes.json: the reference's whole-picture runs on the full-scale pictures of tests/extreme_cases.py; nothing of
+    the oracle's enters the file."""
+    return {"source": "reference in-loop filter and inter prediction callers through oracle/ref_shim_filter.c and oracle/ref_shim_inter.c on "
+                      "tests/extreme_cases.py",
+            "format": "pictures[name][key] = sha256: inputs; the planes after the stage (sao / alf / p + component); regular inter pictures add "
+                      "dmvr = tab_dmvr_mvf, pad bytes zeroed; CIIP: scratch, weights, joint as in ref_inter.json",
+            "pictures": {name: extreme_cases.host_digests(lib, "ref", name) for name in extreme_cases.picture_names()}}
+
+
 def changed_digests(old, new):
     """Groups of `old` that `new` drops or records differently: [] when `new` only adds to `old`."""
     return [f"{slot}/{key}" for slot, grp in old.items() for key, rec in grp.items() if new.get(slot, {}).get(key) != rec]
@@ -162,8 +178,10 @@ def main():
     i_path = ref_inter_cases.GOLDEN_PATH if ref_inter_cases is not None else None
     recon = dumps_passes(generate_recon(lib)) if ref_recon_cases is not None else None
     r_path = ref_recon_cases.GOLDEN_PATH if ref_recon_cases is not None else None
+    extremes = dumps_passes(generate_extremes(lib)) if extreme_cases is not None else None
+    x_path = extreme_cases.GOLDEN_PATH if extreme_cases is not None else None
     if "--check" in sys.argv:
-        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon)):
+        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon), (x_path, extremes)):
             if path is None:
                 continue
             if not os.path.exists(path):
@@ -179,6 +197,8 @@ def main():
             bad += changed_digests(ref_inter_cases.load_golden(), json.loads(inter)["pictures"])
         if r_path and os.path.exists(r_path):
             bad += changed_digests(ref_recon_cases.load_golden(), json.loads(recon)["pictures"])
+        if x_path and os.path.exists(x_path):
+            bad += changed_digests(extreme_cases.load_golden(), json.loads(extremes)["pictures"])
         if bad:
             sys.exit(f"{len(bad)} recorded groups would change or vanish (first: {bad[:4]}): nothing written; --replace if that is meant")
     with open(PATH, "w") as f:
@@ -196,6 +216,10 @@ def main():
         with open(r_path, "w") as f:
             f.write(recon)
         print(f"wrote {r_path}: {len(json.loads(recon)['pictures'])} pictures, {len(recon)} bytes")
+    if x_path:
+        with open(x_path, "w") as f:
+            f.write(extremes)
+        print(f"wrote {x_path}: {len(json.loads(extremes)['pictures'])} pictures, {len(extremes)} bytes")
 
 
 if __name__ == "__main__":
