@@ -206,6 +206,10 @@ BATCH_SIGNATURES = {
     "rec_end_picture":  ("i", "pp"),
     "rec_fill_arena":   ("i", "pp"),
     "rec_bind":         ("i", "pz"),
+    # the unit entry of the recorder: rec_ctu that also takes CIIP units and a vvc355_rec_pu per coding unit, and after end_picture the
+    # cu / tu records with their QP sidecars, the motion records and the four inter-unit lists in raster CTU order
+    "rec_ctu_units":    ("i", "piiippi"),
+    "rec_units":        ("i", "pp"),
 }
 
 
@@ -975,3 +979,25 @@ class RecResult(ctypes.Structure):
 REC_SLICE_DEP_QUANT, REC_SLICE_LMCS = 1, 2
 (REC_E_ARGS, REC_E_STATE, REC_E_PARAMS, REC_E_CTU_RANGE, REC_E_CTU_TWICE, REC_E_CU_RECT, REC_E_TB_RECT, REC_E_SIDE, REC_E_C_IDX, REC_E_LEVELS,
  REC_E_CIIP, REC_E_NOMEM) = range(-1, -13, -1)
+
+
+class RecPu(ctypes.Structure):
+    """Mirror of vvc355_rec_pu (motion = HOST int32: MvFields, control points or the two GPM MvFields, by kind)."""
+    _fields_ = [("motion", ctypes.c_uint64), ("kind", ctypes.c_uint8), ("merge_subblock_flag", ctypes.c_uint8),
+                ("num_sb_x", ctypes.c_uint8), ("num_sb_y", ctypes.c_uint8), ("dmvr_flag", ctypes.c_uint8), ("bdof_flag", ctypes.c_uint8),
+                ("hpel_if_idx", ctypes.c_uint8), ("bcw_idx", ctypes.c_uint8), ("pred_flag", ctypes.c_uint8), ("motion_model_idc", ctypes.c_uint8),
+                ("gpm_partition_idx", ctypes.c_uint8), ("ref_idx", ctypes.c_int8 * 2), ("pad_", ctypes.c_uint8 * 11)]
+
+
+class RecUnitsResult(ctypes.Structure):
+    """Mirror of vvc355_rec_units_result: HOST addresses with the lifetime of RecResult."""
+    _fields_ = [("cu", ctypes.c_uint64), ("cu_qp", ctypes.c_uint64), ("tu", ctypes.c_uint64), ("tu_qp_c", ctypes.c_uint64),
+                ("ctu_first_cu", ctypes.c_uint64), ("ctu_first_tu", ctypes.c_uint64), ("mvf", ctypes.c_uint64), ("ctu_first_mvf", ctypes.c_uint64),
+                ("inter", ctypes.c_uint64), ("affine", ctypes.c_uint64), ("gpm", ctypes.c_uint64), ("ciip", ctypes.c_uint64),
+                ("n_cu", ctypes.c_int32), ("n_tu", ctypes.c_int32), ("n_mvf", ctypes.c_int32), ("n_inter", ctypes.c_int32),
+                ("n_affine", ctypes.c_int32), ("n_gpm", ctypes.c_int32), ("n_ciip", ctypes.c_int32),
+                ("n_inter_jobs", ctypes.c_int32), ("n_affine_jobs", ctypes.c_int32), ("n_gpm_jobs", ctypes.c_int32), ("n_ciip_jobs", ctypes.c_int32),
+                ("ciip_scratch_len", ctypes.c_int32)]
+
+
+RECU_E_ARGS, RECU_E_MIXED, RECU_E_CIIP_SHAPE, RECU_E_MOTION, RECU_E_COUNT = range(-21, -26, -1)

@@ -7,8 +7,15 @@
  * 128, this one — holds an intra unit.  vvc355_rec_end_picture decides those, drops the RESID commands of the blocks that go to the batched
  * passes and the command lists of CTUs left with nothing but MARKs, groups the records (counting sort, CTUs in raster order, decoding order
  * inside a group), numbers the arena slots in list order and moves the packed groups into the same order.
+ *
+ * vvc355_rec_ctu_units is the same walk with two additions.  A CIIP unit gets its PRED + CIIP commands ahead of an inter unit's, every
+ * coded block of it is KEEP, and it makes its CTU one that holds an intra unit.  And every unit leaves its unit records (vvc355_cu_rec,
+ * vvc355_tu_rec, their QP bytes) and its motion records (vvc355_mvf_unit, and a vvc355_inter_pu / _affine_cu / _gpm_cu / _ciip_cu) in
+ * recording order; vvc355_rec_end_picture puts them in raster CTU order and fills the running sums (first_job, scratch_off, link, the
+ * ctu_first tables, the CIIP units' command indices).
  * Plain C11, no HIP, one thread at a time per object.
  */
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -17,6 +24,8 @@
 enum { ST_IDLE, ST_BEGUN, ST_ENDED };
 enum { L_INTRA, L_INTER, L_TS, N_LISTS };
 enum { W_NO, W_YES, W_DEFERRED };
+enum { M_NONE, M_WALK, M_UNITS };                /* which of the two CTU entries the picture goes through */
+enum { U_CU, U_TU, U_MVF, U_INTER, U_AFFINE, U_GPM, U_CIIP, N_UNIT_LISTS };
 enum { N_KEYS = 2 * VVC355_INTER_TB_BINS };      /* the largest key space of the three lists */
 #define NO_SEQ 0xFFFFFFFFu
 
@@ -34,7 +43,16 @@ typedef struct rec_ctu {
     uint32_t cmd_first, cmd_n, blk_first, blk_n, intra_seq;
     uint8_t  seen, has_intra;
     uint8_t  kind;             /* set by end_picture: 0 no commands, 1 LIGHT, 2 the walk writes its luma */
+    uint32_t u_first[N_UNIT_LISTS], u_n[N_UNIT_LISTS];     /* its ranges in the pending unit lists */
 } rec_ctu;
+
+/* a unit list: the records in recording order, and in raster CTU order after end_picture */
+typedef struct rec_list {
+    uint8_t *pend, *out;
+    size_t pend_cap, out_cap, n, elem;
+} rec_list;
+static const size_t unit_elem[N_UNIT_LISTS] = { sizeof(vvc355_cu_rec), sizeof(vvc355_tu_rec), sizeof(vvc355_mvf_unit), sizeof(vvc355_inter_pu),
+                                                sizeof(vvc355_affine_cu), sizeof(vvc355_gpm_cu), sizeof(vvc355_ciip_cu) };
 
 struct vvc355_recorder {
     vvc355_rec_params p;
@@ -56,6 +74,13 @@ struct vvc355_recorder {
     uint32_t *fin;                size_t fin_cap;        /* final record index -> block */
     int16_t *levels;              size_t levels_cap;
     size_t n_rec;
+    /* the unit entry */
+    int mode;
+    rec_list ul[N_UNIT_LISTS];
+    int8_t *cu_qp, *cu_qp_out;    size_t cu_qp_cap, cu_qp_out_cap;
+    int8_t *tu_qp, *tu_qp_out;    size_t tu_qp_cap, tu_qp_out_cap;      /* two bytes a record */
+    int32_t *ctu_first[3];        size_t ctu_first_cap[3];              /* U_CU, U_TU, U_MVF */
+    vvc355_rec_units_result units;
 };
 
 static int grow_(void **p, size_t *cap, size_t n, size_t elem)
@@ -102,6 +127,9 @@ static void restart(vvc355_recorder *r)
     memset(r->tab, 0, 3 * (size_t)r->tab_w * r->tab_h);
     r->seq = 0;
     r->n_pc = r->n_blk = r->n_tmp = r->n_raw = r->n_cmds = r->n_rec = 0;
+    for (int l = 0; l < N_UNIT_LISTS; l++)
+        r->ul[l].n = 0;
+    r->mode = M_NONE;
     r->state = ST_BEGUN;
 }
 
@@ -122,6 +150,12 @@ void vvc355_rec_destroy(vvc355_recorder *r)
         return;
     free(r->ctu); free(r->tab); free(r->pc); free(r->blk); free(r->tmp); free(r->raw);
     free(r->cmds); free(r->cmd_slot); free(r->out_ctu); free(r->order); free(r->recs); free(r->lv); free(r->fin); free(r->levels);
+    for (int l = 0; l < N_UNIT_LISTS; l++) {
+        free(r->ul[l].pend); free(r->ul[l].out);
+    }
+    free(r->cu_qp); free(r->cu_qp_out); free(r->tu_qp); free(r->tu_qp_out);
+    for (int l = 0; l < 3; l++)
+        free(r->ctu_first[l]);
     free(r);
 }
 
@@ -237,8 +271,8 @@ static int record_block(vvc355_recorder *r, int slice_flags, const vvc355_rec_cu
     k->sj = (uint8_t)(scale | jb);
     k->n_elem_log2 = (uint8_t)(lw + lh);
     k->dep[0] = k->dep[1] = -1;
-    k->walk = is_intra ? W_YES : W_NO;
-    if (!is_intra && scale) {
+    k->walk = (is_intra || cu->ciip_flag) ? W_YES : W_NO;       /* a CIIP unit's blocks: its CIIP commands overwrite what a batched pass added */
+    if (k->walk == W_NO && scale) {
         const int xv = cu->x0 & ~((1 << r->ls) - 1), yv = cu->y0 & ~((1 << r->ls) - 1);
         k->walk = W_DEFERRED;
         if (xv > 0)
@@ -317,7 +351,7 @@ static int record_block(vvc355_recorder *r, int slice_flags, const vvc355_rec_cu
     return 0;
 }
 
-static int check_cu(const vvc355_recorder *r, int rs, const vvc355_rec_cu *cu)
+static int check_cu(const vvc355_recorder *r, int rs, const vvc355_rec_cu *cu, int units)
 {
     const vvc355_rec_params *p = &r->p;
     const int ctb = 1 << p->ctb_log2, cx = (rs % r->ncx) << p->ctb_log2, cy = (rs / r->ncx) << p->ctb_log2;
@@ -325,8 +359,11 @@ static int check_cu(const vvc355_recorder *r, int rs, const vvc355_rec_cu *cu)
         return VVC355_REC_E_SIDE;
     if (cu->x0 < cx || cu->y0 < cy || cu->x0 + cu->w > cx + ctb || cu->y0 + cu->h > cy + ctb || cu->x0 + cu->w > p->width || cu->y0 + cu->h > p->height)
         return VVC355_REC_E_CU_RECT;
-    if (cu->ciip_flag)
+    if (cu->ciip_flag && !units)
         return VVC355_REC_E_CIIP;
+    /* a CIIP unit is a single-tree inter unit: only such a unit gets the vvc355_ciip_cu its CIIP commands are paired with */
+    if (cu->ciip_flag && (cu->pred_mode != 0 || cu->tree_type != 0 || cu->w < 4 || cu->h < 4 || cu->w > 64 || cu->h > 64 || cu->w * cu->h < 64))
+        return VVC355_RECU_E_CIIP_SHAPE;
     if (cu->n_tus < 0 || (cu->n_tus > 0 && !cu->tus))
         return VVC355_REC_E_ARGS;
     for (int i = 0; i < cu->n_tus; i++) {
@@ -397,12 +434,186 @@ static int record_predict(vvc355_recorder *r, const vvc355_rec_cu *cu, int i, in
     return push_cmd(r, VVC355_RECON_MARK, 1, x0, y0, w, h, cu, NULL);
 }
 
-int vvc355_rec_ctu(vvc355_recorder *r, int rs, int slice_flags, const vvc355_rec_cu *cus, int n_cus)
+/* ---------------------------------------------------------------------------------------------------------------- one CTU's unit records */
+
+static int tiles16(int v)
+{
+    return (v + 15) >> 4;
+}
+
+/* a zeroed record at the end of pending list l, or NULL */
+static void *unit_push(vvc355_recorder *r, int l)
+{
+    rec_list *L = &r->ul[l];
+    L->elem = unit_elem[l];
+    if (grow_((void **)&L->pend, &L->pend_cap, L->n + 1, L->elem))
+        return NULL;
+    void *p = L->pend + L->n++ * L->elem;
+    memset(p, 0, L->elem);
+    return p;
+}
+
+/* the record predicate of vvc355_mvf_unit_check (include/vvc_mi355.h) for a record the recorder is about to make: its pad_ is 0 and its link
+ * is the recorder's own, which leaves the rules on sides, placement, kind and the affine / GPM bodies */
+static int motion_ok(const vvc355_recorder *r, int rs, int x0, int y0, int w, int h, int kind, int aux, int pf, int gpm_pf0, int gpm_pf1)
+{
+    const int ctb = 1 << r->p.ctb_log2, ox = (rs % r->ncx) << r->p.ctb_log2, oy = (rs / r->ncx) << r->p.ctb_log2;
+    if (w <= 0 || h <= 0 || ((w | h) & 3) || w > 128 || h > 128)
+        return 0;
+    if (x0 < 0 || y0 < 0 || ((x0 | y0) & 3) || x0 + w > r->p.width || y0 + h > r->p.height)
+        return 0;
+    if (x0 < ox || y0 < oy || x0 + w > ox + ctb || y0 + h > oy + ctb)
+        return 0;
+    if (kind == VVC355_MVF_AFFINE)
+        return w >= 8 && h >= 8 && pow2(w) && pow2(h) && (aux == 1 || aux == 2) && (pf & 3);
+    if (kind == VVC355_MVF_GPM)
+        return w >= 8 && h >= 8 && w <= 64 && h <= 64 && w < 8 * h && h < 8 * w && aux <= 63 && (gpm_pf0 == 1 || gpm_pf0 == 2) && (gpm_pf1 == 1 || gpm_pf1 == 2);
+    return kind == VVC355_MVF_PLAIN;
+}
+
+static int mvf_push(vvc355_recorder *r, int x0, int y0, int w, int h, int kind, int aux, const int32_t *body, int n_body, vvc355_mvf_unit **out)
+{
+    vvc355_mvf_unit *u = unit_push(r, U_MVF);
+    if (!u)
+        return VVC355_REC_E_NOMEM;
+    u->x0 = (int16_t)x0, u->y0 = (int16_t)y0, u->w = (uint8_t)w, u->h = (uint8_t)h, u->kind = (uint8_t)kind, u->aux = (uint8_t)aux;
+    if (body)
+        memcpy(u->body, body, sizeof(int32_t) * (size_t)n_body);
+    if (out)
+        *out = u;
+    return 0;
+}
+
+/* the unit records (set_cb_tab / set_tb_tab's call sites) and the motion records (vvc_mvs.c's three storage rules) of one coding unit */
+static int record_unit(vvc355_recorder *r, int rs, int slice, const vvc355_rec_cu *cu, const vvc355_rec_pu *pu)
+{
+    const int chroma = r->p.chroma_format_idc != 0;
+    const int inter = cu->pred_mode != 1 && cu->tree_type != 2;
+    int ret;
+    if (inter && (!pu || !pu->motion))
+        return VVC355_RECU_E_ARGS;
+    if (cu->tree_type != 2) {
+        vvc355_cu_rec *c = unit_push(r, U_CU);
+        if (!c || GROW(r->cu_qp, r->cu_qp_cap, r->ul[U_CU].n))
+            return VVC355_REC_E_NOMEM;
+        c->x0 = (int16_t)cu->x0, c->y0 = (int16_t)cu->y0, c->w = (uint8_t)cu->w, c->h = (uint8_t)cu->h;
+        c->flags = inter ? (uint8_t)((pu->merge_subblock_flag != 0) | (pu->kind == VVC355_MVF_AFFINE) << 1) : 0;
+        r->cu_qp[r->ul[U_CU].n - 1] = cu->qp[0];
+    }
+    for (int tree = cu->tree_type == 2; tree < 1 + (chroma && cu->tree_type != 1); tree++) {
+        for (int i = 0; i < cu->n_tus; i++) {
+            const vvc355_rec_tu *tu = &cu->tus[i];
+            const int both = tu->joint_cbcr_residual_flag && tu->coded_flag[1] && tu->coded_flag[2];
+            vvc355_tu_rec *t = unit_push(r, U_TU);
+            if (!t || GROW(r->tu_qp, r->tu_qp_cap, 2 * r->ul[U_TU].n))
+                return VVC355_REC_E_NOMEM;
+            t->x0 = (int16_t)tu->x0, t->y0 = (int16_t)tu->y0, t->w = (uint8_t)tu->w, t->h = (uint8_t)tu->h;
+            t->flags = tree ? (uint8_t)(0x80 | (tu->coded_flag[1] != 0) << 1 | (tu->coded_flag[2] != 0) << 2 | (tu->joint_cbcr_residual_flag != 0) << 3)
+                            : (uint8_t)(tu->coded_flag[0] != 0);
+            int8_t *q = r->tu_qp + 2 * (r->ul[U_TU].n - 1);
+            q[0] = tree ? cu->qp[both ? 3 : 1] : 0, q[1] = tree ? cu->qp[both ? 3 : 2] : 0;
+        }
+    }
+    if (cu->tree_type == 2)
+        return 0;
+    if (!inter)                                       /* ff_vvc_set_intra_mvf: a zero MvField over the unit */
+        return motion_ok(r, rs, cu->x0, cu->y0, cu->w, cu->h, VVC355_MVF_PLAIN, 0, 0, 0, 0) ?
+               mvf_push(r, cu->x0, cu->y0, cu->w, cu->h, VVC355_MVF_PLAIN, 0, NULL, 0, NULL) : VVC355_RECU_E_MOTION;
+
+    vvc355_mvf_unit *u;
+    if (pu->kind == VVC355_MVF_PLAIN) {
+        const int nx = pu->num_sb_x, ny = pu->num_sb_y;
+        if (cu->ciip_flag && (nx != 1 || ny != 1))
+            return VVC355_RECU_E_CIIP_SHAPE;
+        if (!nx || !ny || cu->w % nx || cu->h % ny)
+            return VVC355_RECU_E_MOTION;
+        const int sw = cu->w / nx, sh = cu->h / ny;
+        if (!motion_ok(r, rs, cu->x0, cu->y0, cu->w, cu->h, VVC355_MVF_PLAIN, 0, 0, 0, 0) || ((sw | sh) & 3))
+            return VVC355_RECU_E_MOTION;
+        for (int sy = 0; sy < ny; sy++)
+            for (int sx = 0; sx < nx; sx++) {
+                if ((ret = mvf_push(r, cu->x0 + sx * sw, cu->y0 + sy * sh, sw, sh, VVC355_MVF_PLAIN, 0, pu->motion + 6 * (sy * nx + sx), 6, &u)))
+                    return ret;
+                if (cu->ciip_flag)
+                    ((uint8_t *)u->body)[offsetof(vvc355_mvfield, ciip_flag)] = 1;
+            }
+        if (cu->ciip_flag) {
+            vvc355_ciip_cu *c = unit_push(r, U_CIIP);
+            if (!c)
+                return VVC355_REC_E_NOMEM;
+            c->x0 = (int16_t)cu->x0, c->y0 = (int16_t)cu->y0, c->cb_width = cu->w, c->cb_height = cu->h;
+            c->hpel_if_idx = pu->hpel_if_idx, c->slice = (uint8_t)slice;
+            c->cmd[0] = c->cmd[1] = c->cmd[2] = 0xFFFFFFFFu;
+        } else {
+            vvc355_inter_pu *c = unit_push(r, U_INTER);
+            if (!c)
+                return VVC355_REC_E_NOMEM;
+            c->x0 = (int16_t)cu->x0, c->y0 = (int16_t)cu->y0, c->cb_width = cu->w, c->cb_height = cu->h;
+            c->num_sb_x = (uint8_t)nx, c->num_sb_y = (uint8_t)ny, c->dmvr_flag = pu->dmvr_flag, c->bdof_flag = pu->bdof_flag;
+            c->hpel_if_idx = pu->hpel_if_idx, c->slice = (uint8_t)slice;
+        }
+        return 0;
+    }
+    if (cu->ciip_flag)
+        return VVC355_RECU_E_CIIP_SHAPE;
+    if (pu->kind == VVC355_MVF_AFFINE) {
+        const int pf = (pu->pred_flag & 3) | (pu->hpel_if_idx & 3) << 2 | (pu->bcw_idx & 15) << 4;
+        if (!motion_ok(r, rs, cu->x0, cu->y0, cu->w, cu->h, VVC355_MVF_AFFINE, pu->motion_model_idc, pf, 0, 0))
+            return VVC355_RECU_E_MOTION;
+        if ((ret = mvf_push(r, cu->x0, cu->y0, cu->w, cu->h, VVC355_MVF_AFFINE, pu->motion_model_idc, pu->motion, 12, &u)))
+            return ret;
+        u->pf = (uint8_t)pf, u->ref_idx[0] = pu->ref_idx[0], u->ref_idx[1] = pu->ref_idx[1];
+        u->link = (uint32_t)r->ul[U_AFFINE].n;        /* its number in recording order until end_picture */
+        vvc355_affine_cu *c = unit_push(r, U_AFFINE);
+        if (!c)
+            return VVC355_REC_E_NOMEM;
+        c->x0 = (int16_t)cu->x0, c->y0 = (int16_t)cu->y0, c->cb_width = cu->w, c->cb_height = cu->h;
+        c->num_sb_x = (uint8_t)(cu->w >> 2), c->num_sb_y = (uint8_t)(cu->h >> 2), c->slice = (uint8_t)slice;
+        return 0;
+    }
+    if (pu->kind == VVC355_MVF_GPM) {
+        vvc355_mvfield part[2];
+        memcpy(part, pu->motion, sizeof(part));
+        if (!motion_ok(r, rs, cu->x0, cu->y0, cu->w, cu->h, VVC355_MVF_GPM, pu->gpm_partition_idx, 0, part[0].pred_flag, part[1].pred_flag))
+            return VVC355_RECU_E_MOTION;
+        if ((ret = mvf_push(r, cu->x0, cu->y0, cu->w, cu->h, VVC355_MVF_GPM, pu->gpm_partition_idx, pu->motion, 12, NULL)))
+            return ret;
+        vvc355_gpm_cu *c = unit_push(r, U_GPM);
+        if (!c)
+            return VVC355_REC_E_NOMEM;
+        c->x0 = (int16_t)cu->x0, c->y0 = (int16_t)cu->y0, c->cb_width = cu->w, c->cb_height = cu->h;
+        c->partition_idx = pu->gpm_partition_idx, c->slice = (uint8_t)slice;
+        memcpy(c->gpm_mv, pu->motion, sizeof(c->gpm_mv));
+        return 0;
+    }
+    return VVC355_RECU_E_MOTION;
+}
+
+/* ff_vvc_predict_ciip (vvc_inter.c:915) as commands: per present component the planar prediction and the blend with the inter part, which
+ * vvc355_ciip_frame_build completes (resid, joint); chroma 2 wide or narrower is not blended (do_ciip, :590) */
+static int record_ciip(vvc355_recorder *r, const vvc355_rec_cu *cu)
+{
+    int ret;
+    for (int c = 0; c < (r->p.chroma_format_idc ? 3 : 1); c++) {
+        if (c && (cu->w >> r->hs) <= 2)
+            continue;
+        if ((ret = push_cmd(r, VVC355_RECON_PRED, c, cu->x0, cu->y0, cu->w, cu->h, cu, NULL)) ||
+            (ret = push_cmd(r, VVC355_RECON_CIIP, c, cu->x0, cu->y0, cu->w, cu->h, cu, NULL)))
+            return ret;
+    }
+    return 0;
+}
+
+static int record_ctu(vvc355_recorder *r, int rs, int slice_flags, const vvc355_rec_cu *cus, int n_cus, int units, int slice, const vvc355_rec_pu *pus)
 {
     if (!r)
         return VVC355_REC_E_ARGS;
     if (r->state != ST_BEGUN)
         return VVC355_REC_E_STATE;
+    if (r->mode != M_NONE && r->mode != (units ? M_UNITS : M_WALK))
+        return refuse(r, VVC355_RECU_E_MIXED);
+    if (units && (slice < 0 || slice > 255))          /* the unit lists carry it in a byte */
+        return refuse(r, VVC355_RECU_E_ARGS);
     if (n_cus < 0 || (n_cus > 0 && !cus))
         return refuse(r, VVC355_REC_E_ARGS);
     if (rs < 0 || rs >= r->ncx * r->ncy)
@@ -411,18 +622,25 @@ int vvc355_rec_ctu(vvc355_recorder *r, int rs, int slice_flags, const vvc355_rec
         return refuse(r, VVC355_REC_E_CTU_TWICE);
     int ret;
     for (int i = 0; i < n_cus; i++)
-        if ((ret = check_cu(r, rs, &cus[i])))
+        if ((ret = check_cu(r, rs, &cus[i], units)))
             return refuse(r, ret);
 
     rec_ctu *t = &r->ctu[rs];
+    r->mode = units ? M_UNITS : M_WALK;
     t->seen = 1;
     t->cmd_first = (uint32_t)r->n_pc, t->blk_first = (uint32_t)r->n_blk;
+    for (int l = 0; l < N_UNIT_LISTS; l++)
+        t->u_first[l] = (uint32_t)r->ul[l].n;
     const size_t plane = (size_t)r->tab_w * r->tab_h;
     const int chroma = r->p.chroma_format_idc != 0;
     for (int n = 0; n < n_cus; n++, r->seq++) {
         const vvc355_rec_cu *cu = &cus[n];
-        if (cu->pred_mode == 1 && !t->has_intra)
+        if ((cu->pred_mode == 1 || cu->ciip_flag) && !t->has_intra)       /* the walk writes a CIIP unit's luma as it writes an intra unit's */
             t->has_intra = 1, t->intra_seq = r->seq;
+        if (units && (ret = record_unit(r, rs, slice, cu, pus ? &pus[n] : NULL)))
+            return refuse(r, ret);
+        if (cu->ciip_flag && (ret = record_ciip(r, cu)))
+            return refuse(r, ret);
         if (cu->tree_type != 2) {                     /* what the parser paints per 4x4 unit for the luma tree */
             for (int y = cu->y0 >> 2; y < (cu->y0 + cu->h + 3) >> 2; y++) {
                 uint8_t *row = r->tab + (size_t)y * r->tab_w + (cu->x0 >> 2);
@@ -453,12 +671,96 @@ int vvc355_rec_ctu(vvc355_recorder *r, int rs, int slice_flags, const vvc355_rec
     }
     t = &r->ctu[rs];
     t->cmd_n = (uint32_t)r->n_pc - t->cmd_first, t->blk_n = (uint32_t)r->n_blk - t->blk_first;
+    for (int l = 0; l < N_UNIT_LISTS; l++) {
+        t->u_n[l] = (uint32_t)r->ul[l].n - t->u_first[l];
+        if (l <= U_MVF && t->u_n[l] > 65535)           /* what the device passes read of one CTU's range */
+            return refuse(r, VVC355_RECU_E_COUNT);
+    }
     return 0;
+}
+
+int vvc355_rec_ctu(vvc355_recorder *r, int rs, int slice_flags, const vvc355_rec_cu *cus, int n_cus)
+{
+    return record_ctu(r, rs, slice_flags, cus, n_cus, 0, 0, NULL);
+}
+
+int vvc355_rec_ctu_units(vvc355_recorder *r, int rs, int slice_flags, int slice, const vvc355_rec_cu *cus, const vvc355_rec_pu *pus, int n_cus)
+{
+    return record_ctu(r, rs, slice_flags, cus, n_cus, 1, slice, pus);
 }
 
 /* ---------------------------------------------------------------------------------------------------------------- the picture */
 
 static const int list_keys[N_LISTS] = { 5, 2 * VVC355_INTER_TB_BINS, 2 * VVC355_TS_TB_CLASSES };
+
+/* the unit lists from recording order into raster CTU order, with what depends on that order: the ctu_first tables, the running job and
+ * scratch sums, the affine records' numbers in the motion records that link them */
+static int units_in_raster_order(vvc355_recorder *r)
+{
+    const int n_ctu = r->ncx * r->ncy, chroma = r->p.chroma_format_idc != 0;
+    vvc355_rec_units_result *o = &r->units;
+    memset(o, 0, sizeof(*o));
+    for (int l = 0; l < N_UNIT_LISTS; l++) {
+        rec_list *L = &r->ul[l];
+        L->elem = unit_elem[l];
+        if (grow_((void **)&L->out, &L->out_cap, L->n + 1, L->elem) || (l <= U_MVF && GROW(r->ctu_first[l], r->ctu_first_cap[l], (size_t)n_ctu + 1)))
+            return -1;
+    }
+    if (GROW(r->cu_qp_out, r->cu_qp_out_cap, r->ul[U_CU].n + 1) || GROW(r->tu_qp_out, r->tu_qp_out_cap, 2 * r->ul[U_TU].n + 2))
+        return -1;
+    size_t at[N_UNIT_LISTS] = { 0 };
+    for (int rs = 0; rs < n_ctu; rs++) {
+        const rec_ctu *t = &r->ctu[rs];
+        if (t->u_n[U_CU])
+            memcpy(r->cu_qp_out + at[U_CU], r->cu_qp + t->u_first[U_CU], t->u_n[U_CU]);
+        if (t->u_n[U_TU])
+            memcpy(r->tu_qp_out + 2 * at[U_TU], r->tu_qp + 2 * (size_t)t->u_first[U_TU], 2 * (size_t)t->u_n[U_TU]);
+        vvc355_mvf_unit *mv = (vvc355_mvf_unit *)r->ul[U_MVF].out + at[U_MVF];
+        for (int l = 0; l < N_UNIT_LISTS; l++) {
+            const rec_list *L = &r->ul[l];
+            if (l <= U_MVF)
+                r->ctu_first[l][rs] = (int32_t)at[l];
+            if (t->u_n[l])
+                memcpy(L->out + at[l] * L->elem, L->pend + t->u_first[l] * L->elem, t->u_n[l] * L->elem);
+        }
+        for (uint32_t i = 0; i < t->u_n[U_MVF]; i++)
+            if (mv[i].kind == VVC355_MVF_AFFINE)
+                mv[i].link = (uint32_t)at[U_AFFINE] + (mv[i].link - t->u_first[U_AFFINE]);
+        for (int l = 0; l < N_UNIT_LISTS; l++)
+            at[l] += t->u_n[l];
+    }
+    for (int l = 0; l <= U_MVF; l++)
+        r->ctu_first[l][n_ctu] = (int32_t)at[l];
+    vvc355_inter_pu *pu = (vvc355_inter_pu *)r->ul[U_INTER].out;
+    for (size_t i = 0; i < at[U_INTER]; i++) {
+        pu[i].first_job = (uint32_t)o->n_inter_jobs;
+        o->n_inter_jobs += pu[i].num_sb_x * pu[i].num_sb_y * tiles16(pu[i].cb_width / pu[i].num_sb_x) * tiles16(pu[i].cb_height / pu[i].num_sb_y);
+    }
+    vvc355_affine_cu *af = (vvc355_affine_cu *)r->ul[U_AFFINE].out;
+    for (size_t i = 0; i < at[U_AFFINE]; i++) {
+        af[i].first_job = (uint32_t)o->n_affine_jobs;
+        o->n_affine_jobs += af[i].num_sb_x * af[i].num_sb_y;
+    }
+    vvc355_gpm_cu *gp = (vvc355_gpm_cu *)r->ul[U_GPM].out;
+    for (size_t i = 0; i < at[U_GPM]; i++) {
+        gp[i].first_job = (uint32_t)o->n_gpm_jobs;
+        o->n_gpm_jobs += tiles16(gp[i].cb_width) * tiles16(gp[i].cb_height) + (chroma ? 2 * tiles16(gp[i].cb_width >> r->hs) * tiles16(gp[i].cb_height >> r->vs) : 0);
+    }
+    vvc355_ciip_cu *ci = (vvc355_ciip_cu *)r->ul[U_CIIP].out;
+    for (size_t i = 0; i < at[U_CIIP]; i++) {
+        const int w = ci[i].cb_width, h = ci[i].cb_height, wc = w >> r->hs, hc = h >> r->vs;
+        ci[i].first_job = (uint32_t)o->n_ciip_jobs, ci[i].scratch_off = (uint32_t)o->ciip_scratch_len;
+        o->n_ciip_jobs += tiles16(w) * tiles16(h) + (chroma ? 2 * tiles16(wc) * tiles16(hc) : 0);
+        o->ciip_scratch_len += w * h + ((chroma && wc > 2) ? 2 * wc * hc : 0);
+    }
+    o->cu = (const vvc355_cu_rec *)r->ul[U_CU].out, o->cu_qp = r->cu_qp_out, o->tu = (const vvc355_tu_rec *)r->ul[U_TU].out, o->tu_qp_c = r->tu_qp_out;
+    o->ctu_first_cu = r->ctu_first[U_CU], o->ctu_first_tu = r->ctu_first[U_TU], o->ctu_first_mvf = r->ctu_first[U_MVF];
+    o->mvf = (const vvc355_mvf_unit *)r->ul[U_MVF].out;
+    o->inter = pu, o->affine = af, o->gpm = gp, o->ciip = ci;
+    o->n_cu = (int32_t)at[U_CU], o->n_tu = (int32_t)at[U_TU], o->n_mvf = (int32_t)at[U_MVF], o->n_inter = (int32_t)at[U_INTER];
+    o->n_affine = (int32_t)at[U_AFFINE], o->n_gpm = (int32_t)at[U_GPM], o->n_ciip = (int32_t)at[U_CIIP];
+    return 0;
+}
 
 int vvc355_rec_end_picture(vvc355_recorder *r, vvc355_rec_result *res)
 {
@@ -552,6 +854,11 @@ int vvc355_rec_end_picture(vvc355_recorder *r, vvc355_rec_result *res)
     }
     memset(r->levels + 16 * (size_t)run, 0, 32);
 
+    if (r->mode != M_WALK && units_in_raster_order(r))
+        return refuse(r, VVC355_REC_E_NOMEM);
+    /* the CIIP unit whose commands come next: both are in raster CTU order; never past the list, whatever the commands say */
+    vvc355_ciip_cu *ciip = (vvc355_ciip_cu *)r->ul[U_CIIP].out, *const ciip_end = ciip ? ciip + r->ul[U_CIIP].n : NULL;
+
     /* commands: CTUs in raster order; a CTU keeps its list when it holds an intra unit or a residual of the walk */
     r->n_cmds = 0;
     for (int rs = 0; rs < n_ctu; rs++) {
@@ -569,6 +876,11 @@ int vvc355_rec_end_picture(vvc355_recorder *r, vvc355_rec_result *res)
                     continue;
                 any_resid = 1;
                 s = k->slot;
+            } else if (c->kind == VVC355_RECON_CIIP) {   /* a CIIP unit's CTU keeps its list: the index is final */
+                if (ciip < ciip_end && c->c_idx == 0 && ciip->cmd[0] != 0xFFFFFFFFu)
+                    ciip++;
+                if (ciip < ciip_end)
+                    ciip->cmd[c->c_idx] = (uint32_t)r->n_cmds;
             }
             r->cmds[r->n_cmds] = *c;
             r->cmds[r->n_cmds].resid = s;
@@ -607,6 +919,20 @@ int vvc355_rec_end_picture(vvc355_recorder *r, vvc355_rec_result *res)
             res->ts_first[ch][q] = first[L_TS][ch * VVC355_TS_TB_CLASSES + q];
     }
     r->state = ST_ENDED;
+    return 0;
+}
+
+int vvc355_rec_units(const vvc355_recorder *r, vvc355_rec_units_result *out)
+{
+    if (!r)
+        return VVC355_REC_E_ARGS;
+    if (!out)
+        return VVC355_RECU_E_ARGS;
+    if (r->state != ST_ENDED)
+        return VVC355_REC_E_STATE;
+    if (r->mode == M_WALK)
+        return VVC355_RECU_E_MIXED;
+    *out = r->units;
     return 0;
 }
 

@@ -13,11 +13,17 @@
  * that holds the luma left of or above its unit's 64x64 unit contains an intra unit.  CTUs arrive in any order (tiles, wavefront), and with
  * CtbSizeY 128 that CTU can be the block's own, so the answer can depend on units parsed later.
  *
- * Out of scope here: CIIP units (refused with VVC355_REC_E_CIIP), the vvc355_cu_rec / vvc355_tu_rec lists and their QP sidecars, the
- * motion-side records, scaling lists, ACT.
+ * With vvc355_rec_ctu_units in place of vvc355_rec_ctu the same walk also takes CIIP units (their PRED + CIIP commands, the vvc355_ciip_cu
+ * list; every coded block of such a unit is KEEP, and their CTU counts as one that holds an intra unit) and records, from one
+ * vvc355_rec_pu per coding unit, what the deblocking and motion side of a picture reads: the vvc355_cu_rec / vvc355_tu_rec lists with their
+ * QP sidecars, the vvc355_mvf_unit list, and the vvc355_inter_pu / vvc355_affine_cu / vvc355_gpm_cu lists with their running job sums, all
+ * grouped per CTU in raster order whatever the order of the calls (vvc355_rec_units after vvc355_rec_end_picture).
+ * Of the statistics, keep counts a CIIP unit's blocks; walk_scaled and late_keep count what the neighbour rule above keeps, as before.
+ *
+ * Out of scope here: scaling lists, ACT; SAO / ALF / deblocking parameters stay with the caller.
  *
  * Threads: a recorder object is used by ONE thread at a time.  A decoder that parses CTUs on several threads serialises its
- * vvc355_rec_ctu calls (or keeps one recorder per picture and a lock around it); different recorder objects are independent.
+ * vvc355_rec_ctu / vvc355_rec_ctu_units calls (or keeps one recorder per picture and a lock around it); different recorder objects are independent.
  */
 #ifndef VVC_MI355_REC_H
 #define VVC_MI355_REC_H
@@ -127,7 +133,7 @@ enum {
     VVC355_REC_E_SIDE = -8,        /* a side that is not a power of two, or above 64 for a coded block / 128 for a coding unit */
     VVC355_REC_E_C_IDX = -9,       /* c_idx above 2, or a chroma block at 4:0:0 */
     VVC355_REC_E_LEVELS = -10,     /* a coded block without levels */
-    VVC355_REC_E_CIIP = -11,       /* a CIIP unit: not recorded yet */
+    VVC355_REC_E_CIIP = -11,       /* a CIIP unit given to vvc355_rec_ctu: vvc355_rec_ctu_units records those */
     VVC355_REC_E_NOMEM = -12
 };
 
@@ -148,6 +154,63 @@ int vvc355_rec_fill_arena(const vvc355_recorder *rec, int32_t *arena);
 /* After end_picture: turns the RESID commands' slots into addresses inside the DEVICE arena at arena_dev (may be called again with another
  * base: the slots are kept aside). */
 int vvc355_rec_bind(vvc355_recorder *rec, uint64_t arena_dev);
+
+/* ---- the unit entry: CIIP units, unit records and motion records (recorder.c, the same object and the same cycle) */
+
+/* one prediction unit, paired with cus[i] by index and not read for intra units (pred_mode 1) or units of the chroma tree; 32 bytes, no
+ * implicit padding.  `motion` is read during the call only:
+ *   VVC355_MVF_PLAIN   num_sb_x * num_sb_y vvc355_mvfield (6 int32 each), row-major over the sub-blocks; one for an ordinary unit
+ *   VVC355_MVF_AFFINE  mi->mv[list][cp] as x, y: int32 [2][3][2]
+ *   VVC355_MVF_GPM     pu->gpm_mv[0], pu->gpm_mv[1]: two vvc355_mvfield */
+typedef struct vvc355_rec_pu {
+    const int32_t *motion;
+    uint8_t  kind;             /* VVC355_MVF_PLAIN / _AFFINE / _GPM */
+    uint8_t  merge_subblock_flag;
+    uint8_t  num_sb_x, num_sb_y;           /* PLAIN: the sub-block grid (1, 1 for an ordinary unit); other kinds: not read */
+    uint8_t  dmvr_flag, bdof_flag, hpel_if_idx, bcw_idx;
+    uint8_t  pred_flag;        /* AFFINE: mi->pred_flag; other kinds carry it in their MvFields */
+    uint8_t  motion_model_idc; /* AFFINE: 1 or 2 */
+    uint8_t  gpm_partition_idx;
+    int8_t   ref_idx[2];       /* AFFINE */
+    uint8_t  pad_[11];
+} vvc355_rec_pu;
+
+/* HOST pointers into the recorder's buffers, with the lifetime of vvc355_rec_result.  Every list is in raster CTU order, decoding order
+ * inside a CTU; the ctu_first_* tables have n_ctus + 1 entries. */
+typedef struct vvc355_rec_units_result {
+    const vvc355_cu_rec *cu;               /* one per coding unit of the luma or single tree; flags = merge_subblock_flag | affine << 1 */
+    const int8_t *cu_qp;                   /* paired by index: qp[0] */
+    const vvc355_tu_rec *tu;               /* a tree-0 record per transform unit of a luma / single-tree unit, then (chroma formats) a tree-1
+                                            * record per transform unit of a chroma / single-tree unit, unit by unit */
+    const int8_t *tu_qp_c;                 /* [n_tu][2]; read for tree-1 records: qp[1], qp[2], or qp[3] twice for a joint unit with both flags */
+    const int32_t *ctu_first_cu, *ctu_first_tu;
+    const vvc355_mvf_unit *mvf;            /* intra unit: PLAIN, zero body; PLAIN: one per sub-block; AFFINE (link = its affine_cu); GPM */
+    const int32_t *ctu_first_mvf;
+    const vvc355_inter_pu *inter;          /* PLAIN inter units that are not CIIP */
+    const vvc355_affine_cu *affine;        /* prof_flags and diff_mv zero: vvc355_mvf_unit_pass writes them */
+    const vvc355_gpm_cu *gpm;
+    const vvc355_ciip_cu *ciip;            /* in command order; cmd[] = indices into vvc355_rec_result.cmds */
+    int32_t  n_cu, n_tu, n_mvf, n_inter, n_affine, n_gpm, n_ciip;
+    int32_t  n_inter_jobs, n_affine_jobs, n_gpm_jobs, n_ciip_jobs;     /* the totals of the running first_job sums */
+    int32_t  ciip_scratch_len;             /* pixels: the total of the running scratch_off sum */
+} vvc355_rec_units_result;
+
+/* refusals of the unit entry; the recorder is then as vvc355_rec_begin_picture left it, as after any refusal */
+enum {
+    VVC355_RECU_E_ARGS = -21,        /* an inter unit without pus, or without motion; slice outside 0..255; a null result */
+    VVC355_RECU_E_MIXED = -22,       /* vvc355_rec_ctu and vvc355_rec_ctu_units in one picture; vvc355_rec_units after a picture of vvc355_rec_ctu */
+    VVC355_RECU_E_CIIP_SHAPE = -23,  /* a CIIP unit with a side outside 4..64 or an area below 64, or one that is not a single-tree PLAIN inter unit of one
+                                      * sub-block */
+    VVC355_RECU_E_MOTION = -24,      /* a motion record vvc355_mvf_unit_check would reject (sides, placement, kind, the affine and GPM rules), or a
+                                      * sub-block grid that does not divide the unit */
+    VVC355_RECU_E_COUNT = -25        /* more than 65535 records of a kind in one CTU */
+};
+
+/* vvc355_rec_ctu that also accepts CIIP units and records the unit and motion lists.  slice = the index the inter drivers' slices[] use;
+ * pus may be null when no unit of the CTU is inter.  A picture goes through ONE of the two entries. */
+int vvc355_rec_ctu_units(vvc355_recorder *rec, int rs, int slice_flags, int slice, const vvc355_rec_cu *cus, const vvc355_rec_pu *pus, int n_cus);
+/* After a vvc355_rec_end_picture that returned 0, for a picture recorded through vvc355_rec_ctu_units: fills *out; returns 0. */
+int vvc355_rec_units(const vvc355_recorder *rec, vvc355_rec_units_result *out);
 
 #ifdef __cplusplus
 }
