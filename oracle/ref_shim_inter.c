@@ -36,6 +36,7 @@
 
 #include "vvc_oracle.h"
 #include "../include/vvc_mi355.h"
+#include "ref_shim_mir.h"
 
 #define REF_API __attribute__((visibility("default")))
 #define PTR(type, addr) ((type *)(uintptr_t)(addr))
@@ -58,6 +59,52 @@ static H266RawSliceHeader raw_sh[MAX_SLICES];
 static RefPicList         rpl[2];
 static VVCFrame           ref_frame[2][MAX_REFS];
 static AVFrame            ref_av[2][MAX_REFS];
+
+/* both lists: an entry without a luma plane stays NULL, which pred_get_refs refuses */
+void ref_inter_wire_refs(const orc_ref_pic *refs, int n_comp, RefPicList rl[2], VVCFrame fr[2][16], AVFrame av[2][16])
+{
+    for (int l = 0; l < 2; l++) {
+        rl[l].nb_refs = MAX_REFS;
+        for (int i = 0; i < MAX_REFS; i++) {
+            const orc_ref_pic *rp = refs + l * 16 + i;
+            if (!rp->plane[0])
+                continue;
+            for (int c = 0; c < n_comp; c++) {
+                av[l][i].data[c]     = PTR(uint8_t, rp->plane[c]);
+                av[l][i].linesize[c] = rp->stride[c];
+            }
+            fr[l][i].frame = &av[l][i];
+            rl[l].ref[i] = &fr[l][i];
+        }
+    }
+}
+
+int ref_inter_wire_slice(const orc_inter_slice *in, int have_lut, SliceContext *s, H266RawSliceHeader *sh, H266RawPPS *rpps, RefPicList *rl)
+{
+    PredWeightTable *w = &s->sh.pwt;
+
+    if (in->weighted_pred && in->weighted_bipred)
+        return -1;
+    if (in->lmcs_used && !have_lut)
+        return -1;
+    s->sh.r = sh;
+    s->rpl  = rl;
+    sh->sh_slice_type = in->weighted_pred ? VVC_SLICE_TYPE_P : in->weighted_bipred ? VVC_SLICE_TYPE_B : VVC_SLICE_TYPE_I;
+    sh->sh_lmcs_used_flag = in->lmcs_used;
+    if (in->weighted_pred)
+        rpps->pps_weighted_pred_flag = 1;
+    if (in->weighted_bipred)
+        rpps->pps_weighted_bipred_flag = 1;
+    w->log2_denom[0] = in->log2_denom[0];
+    w->log2_denom[1] = in->log2_denom[1];
+    for (int l = 0; l < 2; l++)
+        for (int c = 0; c < 3; c++)
+            for (int i = 0; i < MAX_WEIGHTS; i++) {
+                w->weight[l][c][i] = in->weight[l][c][i];
+                w->offset[l][c][i] = in->offset[l][c][i];
+            }
+    return 0;
+}
 
 /* the picture every entry shares: geometry, planes, MvField tables, reference lists, slice headers, forward map */
 static int wire(int bd, const orc_inter_frame *f, int ctb_log2)
@@ -116,21 +163,7 @@ static int wire(int bd, const orc_inter_frame *f, int ctb_log2)
     fc.tab.mvf       = PTR(MvField, f->mvf);
     cur.tab_dmvr_mvf = PTR(MvField, f->dmvr_mvf);
 
-    /* both lists: an entry without a luma plane stays NULL, which pred_get_refs refuses */
-    for (int l = 0; l < 2; l++) {
-        rpl[l].nb_refs = MAX_REFS;
-        for (int i = 0; i < MAX_REFS; i++) {
-            const orc_ref_pic *rp = refs + l * 16 + i;
-            if (!rp->plane[0])
-                continue;
-            for (int c = 0; c < n_comp; c++) {
-                ref_av[l][i].data[c]     = PTR(uint8_t, rp->plane[c]);
-                ref_av[l][i].linesize[c] = rp->stride[c];
-            }
-            ref_frame[l][i].frame = &ref_av[l][i];
-            rpl[l].ref[i] = &ref_frame[l][i];
-        }
-    }
+    ref_inter_wire_refs(refs, n_comp, rpl, ref_frame, ref_av);
     if (f->lmcs_fwd_lut)
         memcpy(fc.ps.lmcs.fwd_lut, PTR(const void, f->lmcs_fwd_lut), ((size_t)1 << bd) << sps.pixel_shift);
     ff_vvc_dsp_init(&fc.vvcdsp, bd);
@@ -141,30 +174,7 @@ static int wire(int bd, const orc_inter_frame *f, int ctb_log2)
 /* slice s of the caller's table -> sc[s]; -1 for a pair of switches no slice type produces */
 static int wire_slice(const orc_inter_frame *f, int s, int have_lut)
 {
-    const orc_inter_slice *in = PTR(const orc_inter_slice, f->slices) + s;
-    PredWeightTable *w = &sc[s].sh.pwt;
-
-    if (in->weighted_pred && in->weighted_bipred)
-        return -1;
-    if (in->lmcs_used && !have_lut)
-        return -1;
-    sc[s].sh.r = &raw_sh[s];
-    sc[s].rpl  = rpl;
-    raw_sh[s].sh_slice_type = in->weighted_pred ? VVC_SLICE_TYPE_P : in->weighted_bipred ? VVC_SLICE_TYPE_B : VVC_SLICE_TYPE_I;
-    raw_sh[s].sh_lmcs_used_flag = in->lmcs_used;
-    if (in->weighted_pred)
-        raw_pps.pps_weighted_pred_flag = 1;
-    if (in->weighted_bipred)
-        raw_pps.pps_weighted_bipred_flag = 1;
-    w->log2_denom[0] = in->log2_denom[0];
-    w->log2_denom[1] = in->log2_denom[1];
-    for (int l = 0; l < 2; l++)
-        for (int c = 0; c < 3; c++)
-            for (int i = 0; i < MAX_WEIGHTS; i++) {
-                w->weight[l][c][i] = in->weight[l][c][i];
-                w->offset[l][c][i] = in->offset[l][c][i];
-            }
-    return 0;
+    return ref_inter_wire_slice(PTR(const orc_inter_slice, f->slices) + s, have_lut, &sc[s], &raw_sh[s], &raw_pps, rpl);
 }
 
 typedef struct UnitHead { int x0, y0, w, h, slice; } UnitHead;

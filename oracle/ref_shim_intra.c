@@ -441,31 +441,12 @@ REF_API int ref_left_available(const MirLocalContext *m, int x, int y, int targe
  * Returns what ff_vvc_reconstruct returned last (0), or -1 for a picture these objects cannot hold: a unit with ciip_flag
  * (ff_vvc_predict_ciip needs the inter machinery), more than MIR_MAX_SLICES slices, a transform unit with more than three blocks,
  * a block beyond 64 samples, a unit outside its CTU.
+ *
+ * The wiring is mir_recon_build / mir_recon_free (declared in ref_shim_mir.h with the arrays), shared with ref_decode_picture of
+ * ref_shim_picture.c, which completes the same objects with the inter machinery and takes units with ciip_flag.
  */
 #include "libavcodec/refstruct.h"
-
-#define MIR_MAX_SLICES 8
-typedef struct MirReconTb { int32_t c_idx, x0, y0, w, h, ts, has_coeffs, min_x, min_y, max_x, max_y, level_off; } MirReconTb;
-typedef struct MirReconTu { int32_t x0, y0, w, h, coded_flag[3], joint, first_tb, n_tbs; } MirReconTu;
-typedef struct MirReconCu {
-    int32_t x0, y0, w, h, pred_mode, tree_type, mode_y, mode_c;
-    int32_t ref_idx, mip_flag, mip_mode, mip_transposed, mip_chroma_direct, isp_type, num_isp, bdpcm[3];
-    int32_t lfnst_idx, apply_lfnst[3], mts_idx, sbt_flag, sbt_horizontal, sbt_pos, coded_flag, ciip_flag, qp[4];
-    int32_t first_tu, n_tus;
-} MirReconCu;
-typedef struct MirReconPic {
-    uint64_t plane[3];
-    uint64_t slice_idx, col_bd, row_bd;            /* int16 per CTB; uint16 per CTB column (+1) / row (+1) */
-    uint64_t slice_dep_quant, slice_lmcs_used;     /* int32 per slice */
-    uint64_t ctu_first_cu, cus, tus, tbs, levels;  /* int32 [n_ctb + 1]; MirReconCu / Tu / Tb arrays; int32 level arena */
-    uint64_t scale_log;                            /* int32 [scale_log_cap][3], or 0 */
-    int32_t  stride[3];
-    int32_t  width, height, bit_depth, chroma_format_idc, ctb_log2;
-    int32_t  wpp, collocated, mts_enabled, explicit_mts_intra, explicit_mts_inter;
-    int32_t  log2_transform_range, min_qp_prime_ts, joint_cbcr_sign, chroma_residual_scale;
-    int32_t  lmcs_min_bin_idx, lmcs_max_bin_idx, lmcs_pivot[17], lmcs_chroma_scale_coeff[16];
-    int32_t  n_slices, n_levels, scale_log_cap, n_scale_log;
-} MirReconPic;
+#include "ref_shim_mir.h"
 
 REF_API int ref_recon_layout(int what)
 {
@@ -505,7 +486,7 @@ static void rc_paint(uint8_t *tab, int pitch, const MirReconCu *m, int v)
         memset(tab + y * pitch + (m->x0 >> 2), v, (size_t)((m->w + 3) >> 2));
 }
 
-REF_API int ref_recon_picture(MirReconPic *p)
+int mir_recon_build(MirReconPic *p, MirReconObjs *o, int ciip)
 {
     const int ctb = 1 << p->ctb_log2, ncx = (p->width + ctb - 1) >> p->ctb_log2, ncy = (p->height + ctb - 1) >> p->ctb_log2;
     const int pitch = (p->width + 3) >> 2, units = pitch * ((p->height + 3) >> 2);
@@ -517,8 +498,8 @@ REF_API int ref_recon_picture(MirReconPic *p)
     uint8_t *tabs = NULL;
     int *levels = NULL;
     CTU *ctus = NULL;
-    int ret = -1;
 
+    memset(o, 0, sizeof(*o));
     p->n_scale_log = 0;
     if (p->n_slices < 1 || p->n_slices > MIR_MAX_SLICES || p->ctb_log2 < 5 || p->ctb_log2 > 7 || p->chroma_format_idc < 0 || p->chroma_format_idc > 3 ||
         (p->bit_depth != 8 && p->bit_depth != 10 && p->bit_depth != 12))
@@ -598,7 +579,7 @@ REF_API int ref_recon_picture(MirReconPic *p)
             const MirReconCu *m = &cus[i];
             CodingUnit *u;
             TransformUnit **tlink;
-            if (m->ciip_flag || m->n_tus < 0 || m->w < 1 || m->h < 1 || m->x0 < 0 || m->y0 < 0 || m->x0 + m->w > p->width || m->y0 + m->h > p->height ||
+            if ((m->ciip_flag && (!ciip || m->pred_mode || m->tree_type)) || m->n_tus < 0 || m->w < 1 || m->h < 1 || m->x0 < 0 || m->y0 < 0 || m->x0 + m->w > p->width || m->y0 + m->h > p->height ||
                 (m->x0 >> p->ctb_log2) != rs % ncx || (m->y0 >> p->ctb_log2) != rs / ncx || m->w > ctb || m->h > ctb)
                 goto done;
             u = ff_refstruct_allocz(sizeof(*u));
@@ -611,6 +592,7 @@ REF_API int ref_recon_picture(MirReconPic *p)
             u->x0 = m->x0; u->y0 = m->y0; u->cb_width = m->w; u->cb_height = m->h;
             u->pred_mode  = m->pred_mode ? MODE_INTRA : MODE_INTER;
             u->coded_flag = (uint8_t)m->coded_flag;
+            u->ciip_flag  = (uint8_t)m->ciip_flag;
             u->sbt_flag = (uint8_t)m->sbt_flag; u->sbt_horizontal_flag = (uint8_t)m->sbt_horizontal; u->sbt_pos_flag = (uint8_t)m->sbt_pos;
             u->lfnst_idx = m->lfnst_idx;
             u->mts_idx   = (MtsIdx)m->mts_idx;
@@ -673,24 +655,44 @@ REF_API int ref_recon_picture(MirReconPic *p)
         }
     }
 
-    ret = 0;
-    for (int rs = 0; rs < ncx * ncy && !ret; rs++) {
+    o->lc = &lc; o->fc = &fc; o->sps = &sps; o->pps = &pps; o->sc = rc_sc; o->sh = rc_sh;
+    o->ctus = ctus; o->ncx = ncx; o->n_ctb = ncx * ncy; o->tabs = tabs; o->levels = levels;
+    return 0;
+
+done:
+    o->ctus = ctus; o->n_ctb = ncx * ncy; o->tabs = tabs; o->levels = levels;
+    mir_recon_free(o);
+    return -1;
+}
+
+void mir_recon_free(MirReconObjs *o)
+{
+    if (o->ctus)
+        for (int rs = 0; rs < o->n_ctb; rs++)
+            ff_vvc_ctu_free_cus(&o->ctus[rs]);
+    free(o->ctus);
+    free(o->levels);
+    free(o->tabs);
+    memset(o, 0, sizeof(*o));
+    rc_pic = NULL;
+}
+
+REF_API int ref_recon_picture(MirReconPic *p)
+{
+    MirReconObjs o;
+    int ret = 0;
+
+    if (mir_recon_build(p, &o, 0))
+        return -1;
+    for (int rs = 0; rs < o.n_ctb && !ret; rs++) {
         const int s = fc.tab.slice_idx[rs];
         if (s < 0 || s >= p->n_slices) {
             ret = -1;
             break;
         }
         lc.sc = &rc_sc[s];
-        ret = shimdup_reconstruct(&lc, rs, rs % ncx, rs / ncx);
+        ret = shimdup_reconstruct(&lc, rs, rs % o.ncx, rs / o.ncx);
     }
-
-done:
-    if (ctus)
-        for (int rs = 0; rs < ncx * ncy; rs++)
-            ff_vvc_ctu_free_cus(&ctus[rs]);
-    free(ctus);
-    free(levels);
-    free(tabs);
-    rc_pic = NULL;
+    mir_recon_free(&o);
     return ret;
 }

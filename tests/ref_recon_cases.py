@@ -501,15 +501,11 @@ def bind_reference(lib):
                                                            MirReconPic.stride.offset, MirReconPic.n_slices.offset], "the shim's arrays and their mirror differ"
 
 
-def run_reference(lib, pic):
-    """ff_vvc_reconstruct over the picture: (return value, planes, scale log {(x_vpdu, y_vpdu): chroma_scale}, units logged with two values)."""
-    bind_reference(lib)
+def mirror(pic, planes, log):
+    """(MirReconPic over `planes` and the int32 [n][3] scale log, the arrays it points to: keep them while it is used)."""
     first, cus, tus, tbs, levels = shim_arrays(pic)
-    planes = [np.ascontiguousarray(p).copy() for p in pic.planes]
-    n_sl = len(pic.slices)
     dep, used = np.array([s[0] for s in pic.slices], np.int32), np.array([s[1] for s in pic.slices], np.int32)
     col, row = pic.col_bd.astype(np.uint16), pic.row_bd.astype(np.uint16)
-    log = np.zeros((4 * len(tbs) + 4, 3), np.int32)
     m = MirReconPic()
     for c in range(3):
         m.plane[c], m.stride[c] = planes[c].ctypes.data, planes[c].strides[0]
@@ -524,14 +520,30 @@ def run_reference(lib, pic):
         m.lmcs_pivot[i] = pic.model.pivot[i]
     for i in range(16):
         m.lmcs_chroma_scale_coeff[i] = pic.model.chroma_scale_coeff[i]
-    m.n_slices, m.n_levels, m.scale_log_cap = n_sl, len(levels), len(log)
+    m.n_slices, m.n_levels, m.scale_log_cap = len(pic.slices), len(levels), len(log)
+    return m, (dep, used, col, row)
+
+
+def scales_of(log, n):
+    """The first n entries of a scale log: ({(x_vpdu, y_vpdu): chroma_scale}, units logged with two values)."""
+    scales, twice = {}, []
+    for x, y, s in log[:n].tolist():
+        if scales.setdefault((x, y), s) != s:
+            twice.append((x, y))
+    return scales, twice
+
+
+def run_reference(lib, pic):
+    """ff_vvc_reconstruct over the picture: (return value, planes, scale log {(x_vpdu, y_vpdu): chroma_scale}, units logged with two values)."""
+    bind_reference(lib)
+    levels = shim_arrays(pic)[4]
+    planes = [np.ascontiguousarray(p).copy() for p in pic.planes]
+    log = np.zeros((4 * len(shim_arrays(pic)[3]) + 4, 3), np.int32)
+    m, _keep = mirror(pic, planes, log)
     before = levels.copy()
     ret = lib.ref_recon_picture(ctypes.byref(m))
     assert np.array_equal(levels, before) and m.n_scale_log <= len(log)
-    scales, twice = {}, []
-    for x, y, s in log[:m.n_scale_log].tolist():
-        if scales.setdefault((x, y), s) != s:
-            twice.append((x, y))
+    scales, twice = scales_of(log, m.n_scale_log)
     return ret, planes, scales, twice
 
 
@@ -807,8 +819,9 @@ def bind_oracle(orc):
     orc.orc_recon_frame_pass.restype = None
 
 
-def oracle_side(orc, d):
-    """The derived inputs through the oracle's pieces in INTEGRATION.md's order: (planes, scale table or None, arena)."""
+def oracle_side(orc, d, scale_table=None):
+    """The derived inputs through the oracle's pieces in INTEGRATION.md's order: (planes, scale table or None, arena).  scale_table: a table
+    to scale the routed blocks with in place of the one orc_lmcs_vpdu_scale_pass gives (a sensitivity check of ref_picture_cases)."""
     bind_oracle(orc)
     pic, tp = d.pic, d.tpic
     bd, isz = pic.bd, pic.isz
@@ -825,6 +838,8 @@ def oracle_side(orc, d):
             f = scale_frame(pic, planes[0].ctypes.data, pic.width * isz, table.ctypes.data, ctypes.addressof(pic.model), pic.slice_idx.ctypes.data,
                             pic.col_bd.ctypes.data, pic.row_bd.ctypes.data)
             orc.orc_lmcs_vpdu_scale_pass(bd, ctypes.byref(f))
+            if scale_table is not None:
+                table[:] = np.asarray(scale_table, np.int16).ravel()
         for s, off in rest:
             if (s["c_idx"] > 0) != ch:
                 continue

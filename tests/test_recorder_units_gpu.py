@@ -10,6 +10,7 @@ the existing passes, and the result is compared with the oracle on inputs derive
   motion lists    the vvc355_mvf_unit list through vvc355_mvf_unit_pass: every byte of the MvField table and of the affine records against
                   the numpy of mvf_unit_cases applied to the units.
 
+The recorded picture on the device (RecordedCiip) and the chained oracle (ciip_oracle, inter_oracle) are tests/recorder_chain_cases.py's.
 Before any launch the recorder's output is compared with the expectation (what tests/test_recorder_units_cpu.py asserts) and the ticket
 order is checked by vvc355_recon_order_check: a malformed order makes the walk wait forever, so nothing unchecked reaches the device."""
 import ctypes
@@ -20,15 +21,14 @@ import pytest
 
 import bs_cases
 import bs_rec_cases as brc
-import ciip_frame_cases as cf
-import inter_tb_cases as tc
 import mvf_unit_cases as mu
 import picture_cases as pcs
 import qp_rec_cases as qc
-import recorder_cases as rk
 import recorder_units_cases as uc
+import recorder_chain_cases as ch
 import ref_recon_cases as rc
 from ffvvc_amd import abi, batch
+from recorder_chain_cases import RecordedCiip, ciip_oracle, inter_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -42,153 +42,7 @@ def _listed(name):
     return _derived[name]
 
 
-def _checked_record(dev, pic, d, rec=None, order=None):
-    o = uc.record(dev, pic, True, rec=rec, order=order)
-    bad = rk.differences(dev, pic, d, o, True) + uc.unit_differences(pic, d, o)
-    assert not bad, f"{pic.name}: {bad} differ from the expectation: not launched"
-    assert pcs.order_check(dev, o.ctus, pic.ncx, pic.ncy, o.order) == 0 and rc.order_defect(o.ctus, pic.ncx, pic.ncy, o.order) is None, "not launched"
-    return o
-
-
 # ---------------------------------------------------------------------------------------------------------------- CIIP pictures
-
-def ciip_inputs(pic, o_or_e, cmds):
-    """The ciip_frame_cases.CiipPicture of a recorded picture: geometry, the MvField table painted from the units, one vvc355_inter_slice per
-    slice (default weighting, lmcs_used = the slice's flag), the vvc355_ciip_cu list and the command array."""
-    p = cf.CiipPicture(pic.width, pic.height, pic.ctb_log2, pic.idc, pic.isz)
-    p.bd = pic.bd
-    p.mvf = uc.paint_mvf(pic, np.zeros((pic.height // 4, pic.width // 4), mu.MVF_DT))
-    p.slice_idx, p.col_bd, p.row_bd = pic.slice_idx, pic.col_bd, pic.row_bd
-    p.n_slices = len(pic.slices)
-    p.slices = (abi.InterSlice * p.n_slices)()
-    for i, sl in enumerate(pic.slices):
-        p.slices[i].lmcs_used = int(sl[1])
-    p.cus, p.n_jobs, p.scratch_len = o_or_e.ciip, o_or_e.totals["n_ciip_jobs"], o_or_e.totals["ciip_scratch_len"]
-    p.cmds = cmds
-    return p
-
-
-class RecordedCiip:
-    """One picture with CIIP units recorded and uploaded; the stages' frames are filled from the two results."""
-
-    def __init__(self, dev, pic, d, order=None, d_mvf=None):
-        """d_mvf: the device MvField table the CIIP stage reads (by default the table painted from the units, uploaded)."""
-        k = self.k = pcs.Keep()
-        self.dev, self.pic = dev, pic
-        rec = dev.vvc355_rec_create()
-        try:
-            o = self.o = _checked_record(dev, pic, d, rec=rec, order=order)
-            self.d_arena = k.up(o.arena if o.arena_len else np.zeros(4, np.int32))
-            assert dev.vvc355_rec_bind(rec, self.d_arena.ptr) == 0
-            cmds = rk._copy(o.res.cmds, o.res.n_cmds, rk.CMD)
-        finally:
-            dev.vvc355_rec_destroy(rec)
-        assert len(o.u.ciip) > 5 and o.u.totals["ciip_scratch_len"] > 0
-        res, bd = o.res, pic.bd
-        self.host_planes = [tc.pitched(p) for p in pic.planes]
-        self.d_planes = [k.up(p) for p in self.host_planes]
-        strides = self.strides = [p.shape[1] * pic.isz for p in self.host_planes]
-        d_slice, d_col, d_row = (k.up(a) for a in (pic.slice_idx, pic.col_bd, pic.row_bd))
-        d_model = k.up(np.frombuffer(bytes(pic.model), np.uint8))
-        d_levels = k.up(o.levels)
-        n_i, n_e, n_s = res.n_intra, res.n_inter, res.n_ts
-
-        def side(first, n):
-            return k.up(o.lv[first:first + n].view(np.uint8) if n else np.zeros(16, np.uint8)).ptr
-
-        self.scaled = bool(pic.chroma_scale_flag)
-        self.d_table = k.up(np.full(d.tpic.ux * d.tpic.uy, -1, np.int16))
-        st = {}
-        if n_i:
-            f = abi.IntraTbFrame()
-            f.tus, f.coeffs, f.n_tus = k.up(o.intra).ptr, self.d_arena.ptr, n_i
-            for c in range(6):
-                f.class_first[c] = res.class_first[c]
-            f.range, f.bd = pic.rbits, bd
-            f.lv, f.levels = side(0, n_i), d_levels.ptr
-            st["intra_tb"] = k.frame(f)
-        for name, ty, recs, n, first, first_lv in (("inter_tb", abi.InterTbFrame, o.inter, n_e, res.bin_first, n_i),
-                                                   ("ts_tb", abi.TsTbFrame, o.ts, n_s, res.ts_first, n_i + n_e)):
-            if not n:
-                continue
-            f = ty()
-            f.tus, f.coeffs, f.n_tus = k.up(recs).ptr, self.d_arena.ptr, n
-            for c in range(3):
-                f.plane[c], f.stride[c] = self.d_planes[c].ptr, strides[c]
-            f.width, f.height, f.hs, f.vs, f.size_y, f.range, f.bd = pic.width, pic.height, pic.hs, pic.vs, pic.size_y, pic.rbits, bd
-            f.scale_table = self.d_table.ptr if self.scaled else 0
-            dst = f.bin_first if name == "inter_tb" else f.class_first
-            for ch in range(2):
-                for b in range(len(first[ch])):
-                    dst[ch][b] = first[ch][b]
-            f.lv, f.levels = side(first_lv, n), d_levels.ptr
-            st[name] = k.frame(f)
-        if self.scaled:
-            st["lmcs_scale"] = k.frame(rc.scale_frame(pic, self.d_planes[0].ptr, strides[0], self.d_table.ptr, d_model.ptr, d_slice.ptr, d_col.ptr, d_row.ptr))
-        d_state = batch.DeviceBuffer(dev.vvc355_recon_state_bytes(pic.ncx * pic.ncy))
-        k.keep.append(d_state)
-        d_cmds = k.up(cmds)
-        st["recon"] = k.frame(rc.recon_frame(pic, None, [b.ptr for b in self.d_planes], strides, d_cmds.ptr, k.up(o.ctus).ptr, k.up(o.order).ptr,
-                                             d_state.ptr, d_slice.ptr, d_col.ptr, d_row.ptr, d_model.ptr if self.scaled else 0, n_work=res.n_work))
-        # the CIIP stage: the recorder's records, the SAME command array
-        p = self.p = ciip_inputs(pic, o.u, cmds)
-        rng = np.random.default_rng([uc.SEED, pic.bd])
-        self.dims, self.refs, self.lut = cf.pictures(rng, p, bd)
-        d_ref = [[[k.up(batch.to_pitched(self.refs[l][r][c])) for c in range(3)] for r in range(2)] for l in range(2)]
-        d_reft = k.up(np.frombuffer(bytes(cf.ref_table([[[d_ref[l][r][c].ptr for c in range(3)] for r in range(2)] for l in range(2)], strides)), np.uint8))
-        d_jobs = batch.DeviceBuffer(max(1, p.n_jobs) * cf.BIPRED_JOB_DT.itemsize)
-        k.keep.append(d_jobs)
-        d_scratch = k.up(np.zeros(p.scratch_len, pic.planes[0].dtype))
-        d_sl, d_lut = k.up(np.frombuffer(bytes(p.slices), np.uint8)), k.up(self.lut)
-        st["ciip"] = k.frame(p.frame(p.pic([b.ptr for b in self.d_planes], strides, (d_mvf if d_mvf is not None else k.up(p.mvf)).ptr, d_reft.ptr,
-                                           d_sl.ptr, d_lut.ptr),
-                                     k.up(p.cus).ptr, d_jobs.ptr, d_scratch.ptr, d_cmds.ptr, d_slice.ptr, d_col.ptr, d_row.ptr))
-        self.d_reft, self.d_slices, self.d_lut, self.d_maps, self.strides = d_reft, d_sl, d_lut, (d_slice, d_col, d_row), strides
-        self.stages = st
-
-    def run_entries(self):
-        dev, st, bd = self.dev, self.stages, self.pic.bd
-        call = lambda name, fn, *a: fn(None, st[name][0], ctypes.addressof(st[name][1]), *a) if name in st else 0      # noqa: E731
-        assert dev.vvc355_ciip_frame_pass(None, bd, st["ciip"][0], ctypes.addressof(st["ciip"][1])) == 0
-        assert call("intra_tb", dev.vvc355_intra_tb_pass) == 0
-        if self.scaled:
-            assert call("inter_tb", dev.vvc355_inter_tb_pass, 1) == 0
-            assert call("ts_tb", dev.vvc355_ts_tb_pass, 1) == 0
-            dev.vvc355_lmcs_vpdu_scale_pass(None, bd, st["lmcs_scale"][0], ctypes.addressof(st["lmcs_scale"][1]))
-            assert call("inter_tb", dev.vvc355_inter_tb_pass, 2) == 0
-            assert call("ts_tb", dev.vvc355_ts_tb_pass, 2) == 0
-        else:
-            assert call("inter_tb", dev.vvc355_inter_tb_pass, 3) == 0
-            assert call("ts_tb", dev.vvc355_ts_tb_pass, 3) == 0
-        dev.vvc355_recon_frame_pass(None, bd, st["recon"][0], ctypes.addressof(st["recon"][1]))
-
-    def result(self):
-        self.dev.vvc355_stream_sync(None)
-        assert self.dev.vvc355_last_error() == 0
-        planes = [b.to_host(h.dtype, h.shape) for b, h in zip(self.d_planes, self.host_planes)]
-        for c, (g, h, p) in enumerate(zip(planes, self.host_planes, self.pic.planes)):
-            assert np.array_equal(g[:, p.shape[1]:], h[:, p.shape[1]:]), f"component {c}: the pitch padding was written"
-        return [g[:, :p.shape[1]] for g, p in zip(planes, self.pic.planes)]
-
-
-def ciip_oracle(orc, pic, d, e, refs, lut, dims, start=None):
-    """The chained oracle: the inter parts of the CIIP units (orc_bipred_block on the expected jobs, unblended chroma straight onto the
-    planes), then ref_recon_cases.oracle_side on those planes with the CIIP commands completed as the builder completes them."""
-    planes = [np.ascontiguousarray(p).copy() for p in (start or pic.planes)]
-    p = ciip_inputs(pic, e, d.cmds)
-    scratch = np.zeros(p.scratch_len, planes[0].dtype)
-    jobs = cf.expect_jobs(p, lambda c: (planes[c].ctypes.data, dims[c][0] * pic.isz), lambda l, r, c: (refs[l][r][c].ctypes.data, dims[c][0] * pic.isz),
-                          scratch.ctypes.data, lut.ctypes.data)
-    assert (jobs["w"] > 0).all(), "a CIIP record the builder would reject"
-    cf.call(orc.orc_bipred_block, pic.bd, jobs)
-    d2, pic2 = SimpleNamespace(**vars(d)), SimpleNamespace(**vars(pic))
-    pic2.planes = planes
-    d2.pic, d2.cmds = pic2, cf.expect_cmds(p, scratch.ctypes.data)
-    is_ciip = d2.cmds["kind"] == abi.RECON_CIIP
-    assert is_ciip.sum() >= len(p.cus) and d2.cmds["resid"][is_ciip].all() and d2.cmds["joint"][is_ciip].all()
-    out, _table, _arena = rc.oracle_side(orc, d2)
-    return out
-
 
 @pytest.mark.parametrize("name", uc.GPU_CIIP)
 def test_ciip_pictures_reproduce_the_oracle(dev, orc, name):
@@ -260,7 +114,7 @@ def run_bs_rec(dev, t, u):
 def test_unit_lists_give_the_deblocking_tables(dev, orc, name):
     pic, d = _listed(name)
     assert pic.ctb_log2 == {"V64": 6, "V128": 7}[name] and pic.idc
-    o = _checked_record(dev, pic, d)
+    o = ch.checked_record(dev, pic, d)
     u = o.u
     t = bs_tables(pic)
     want = brc.expected(t, bs_cases.run_oracle(orc, t))
@@ -278,7 +132,7 @@ def test_unit_lists_give_the_deblocking_tables(dev, orc, name):
 @pytest.mark.parametrize("name", ["U2", "U5"])
 def test_motion_lists_give_the_mvfield_table(dev, name):
     pic, d = _listed(name)
-    o = _checked_record(dev, pic, d)
+    o = ch.checked_record(dev, pic, d)
     u = o.u
     assert len(u.affine) > 2 and (u.mvf["kind"] == mu.GPM).any() and (u.mvf["kind"] == mu.AFFINE).any()
     g = mu.Geo(pic.width, pic.height, pic.ctb_log2)
@@ -294,49 +148,8 @@ def test_motion_lists_give_the_mvfield_table(dev, name):
 
 # ---------------------------------------------------------------------------------------------------------------- one whole picture
 
-def _gpm_golden():
-    import os
-    return np.load(os.path.join(rc.ROOT, "tests", "golden", "gpm_tables.npz"))
-
-
-def inter_oracle(orc, pic, e, mvf, aff, refs, lut, dims, slices, planes):
-    """The three kinds of inter units that predict onto the picture, on host planes in place: orc_inter_frame_pass on the vvc355_inter_pu
-    list, then pred_affine_blk / pred_gpm_blk as affine_gpm_cases restates them, through the oracle's block functions."""
-    import affine_gpm_cases as agc
-    isz, bd = pic.isz, pic.bd
-    strides = [dm[0] * isz for dm in dims]
-    reft = cf.ref_table([[[refs[l][r][c].ctypes.data for c in range(3)] for r in range(2)] for l in range(2)], strides)
-    plane = lambda c: (planes[c].ctypes.data, strides[c])                                # noqa: E731
-    ref = lambda l, r, c: (refs[l][r][c].ctypes.data, strides[c])                        # noqa: E731
-    n = e.totals["n_inter_jobs"]
-    jl, jc, recs = np.zeros(max(1, n), cf.BIPRED_JOB_DT), np.zeros(max(1, 2 * n), cf.BIPRED_JOB_DT), np.zeros((max(1, n), 8), np.int32)
-    pus = np.ascontiguousarray(e.inter)
-    f = abi.InterFrame()
-    for c in range(3):
-        f.dst[c], f.dst_stride[c] = plane(c)
-    f.mvf, f.refs, f.pus, f.slices = mvf.ctypes.data, ctypes.addressof(reft), pus.ctypes.data, ctypes.addressof(slices)
-    f.jobs_luma, f.jobs_chroma, f.records, f.lmcs_fwd_lut = jl.ctypes.data, jc.ctypes.data, recs.ctypes.data, lut.ctypes.data
-    f.mvf_stride, f.n_pus, f.n_jobs, f.width, f.height = pic.width // 4, len(pus), n, pic.width, pic.height
-    f.hs, f.vs, f.chroma_format_idc, f.pixel_shift = pic.hs, pic.vs, pic.idc, int(isz == 2)
-    orc.orc_inter_frame_pass.argtypes, orc.orc_inter_frame_pass.restype = [ctypes.c_int, ctypes.POINTER(abi.InterFrame)], None
-    orc.orc_inter_frame_pass(bd, ctypes.byref(f))
-    w = agc.AffineGpmWork.__new__(agc.AffineGpmWork)
-    w.width, w.height, w.hs, w.vs, w.chroma, w.isz, w.mvf, w.slices = pic.width, pic.height, pic.hs, pic.vs, True, isz, mvf, slices
-    w.aff, w.n_aff_jobs = aff.view(agc.AFFINE_CU_DT), e.totals["n_affine_jobs"]
-    w.gpm, w.n_gpm_jobs = np.ascontiguousarray(e.gpm).view(agc.GPM_CU_DT), e.totals["n_gpm_jobs"]
-    golden = _gpm_golden()
-    masks = np.ascontiguousarray(golden["ff_vvc_gpm_weights"])
-    a_l, a_c = w.expect_affine(plane, ref, lambda u: w.aff.ctypes.data + u * agc.AFFINE_CU_DT.itemsize, lut.ctypes.data)
-    g = w.expect_gpm(plane, ref, lut.ctypes.data, masks.ctypes.data, golden)
-    agc.call(orc.orc_affine_block, bd, a_l)
-    agc.call(orc.orc_bipred_block, bd, a_c)
-    agc.call(orc.orc_gpm_block, bd, g)
-    return planes
-
-
 def _whole_picture(dev, orc, pic, d, order):
     """The picture through vvc355_mvf_unit_pass and ONE vvc355_picture_pass, every list the recorder's: (tables and planes got, the same wanted)."""
-    import affine_gpm_cases as agc
     import ref_pass_cases as pc
     from test_picture_gpu import _filter_stages
     from test_ref_passes_gpu import Device, _download
@@ -348,23 +161,10 @@ def _whole_picture(dev, orc, pic, d, order):
     d_mvf = dv.up(np.full((g.th, g.tw, 24), 0xEE, np.uint8))
     r = RecordedCiip(dev, pic, d, order=order, d_mvf=d_mvf)
     o, u, k = r.o, r.o.u, r.k
-    d_aff = k.up(u.affine)
-    mf = mu.unit_frame(g, k.up(u.mvf).ptr, len(u.mvf), k.up(u.first_mvf).ptr, d_mvf.ptr, g.tw, d_aff.ptr, len(u.affine))
-    assert dev.vvc355_mvf_unit_pass(None, k.up(np.frombuffer(bytes(mf), np.uint8)).ptr, ctypes.addressof(mf)) == 0
-    st = dict(r.stages)
+    mf, inter_stages = r.motion_stages(d_mvf)
+    assert dev.vvc355_mvf_unit_pass(None, mf[0], ctypes.addressof(mf[1])) == 0
+    st = dict(r.stages, **inter_stages)
     planes_ptr, strides = [b.ptr for b in r.d_planes], r.strides
-    base = r.p.pic(planes_ptr, strides, d_mvf.ptr, r.d_reft.ptr, r.d_slices.ptr, r.d_lut.ptr)
-    n = u.totals["n_inter_jobs"]
-    fi = abi.InterFrame.from_buffer_copy(bytes(base))
-    fi.pus, fi.n_pus, fi.n_jobs = k.up(u.inter).ptr, len(u.inter), n
-    scratch = lambda nbytes: k.up(np.zeros(max(64, nbytes), np.uint8)).ptr               # noqa: E731
-    fi.jobs_luma, fi.jobs_chroma, fi.records = scratch(n * cf.BIPRED_JOB_DT.itemsize), scratch(2 * n * cf.BIPRED_JOB_DT.itemsize), scratch(32 * n)
-    na, ng = u.totals["n_affine_jobs"], u.totals["n_gpm_jobs"]
-    fa = abi.AffineFrame(pic=base, cus=d_aff.ptr, jobs_luma=scratch(na * agc.AFFINE_JOB_DT.itemsize),
-                         jobs_chroma=scratch(2 * (na >> (pic.hs + pic.vs)) * cf.BIPRED_JOB_DT.itemsize), n_cus=len(u.affine), n_jobs=na)
-    fg = abi.GpmFrame(pic=base, cus=k.up(u.gpm).ptr, jobs=scratch(ng * agc.GPM_JOB_DT.itemsize), n_cus=len(u.gpm), n_jobs=ng)
-    assert len(u.inter) and len(u.affine) and len(u.gpm) and len(u.ciip)
-    st.update(inter=k.frame(fi), affine=k.frame(fa), gpm=k.frame(fg))
     # the deblocking side: the recorder's cu / tu lists and sidecars, the table the motion pass wrote
     t = bs_tables(pic, 0, 0)
     dbp = (2 * rng.integers(-12, 13, size=(t.cw * t.ch, 6))).astype(np.int8)

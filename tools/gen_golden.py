@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/ref_slots.json, tests/golden/ref_passes.json, tests/golden/ref_inter.json, tests/golden/ref_recon.json and
-tests/golden/ref_extremes.json (the full-scale pictures of tests/extreme_cases.py, in the format of ref_passes.json / ref_inter.json): SHA-256
+"""Regenerate tests/golden/ref_slots.json, tests/golden/ref_passes.json, tests/golden/ref_inter.json, tests/golden/ref_recon.json,
+tests/golden/ref_picture.json and tests/golden/ref_extremes.json (the full-scale pictures of tests/extreme_cases.py, in the format of ref_passes.json / ref_inter.json): SHA-256
 digests of what the reference's own C path computes on the case lists of tests/ref_cases.py, of what its in-loop filter callers compute on
 the pictures of tests/ref_pass_cases.py, of what its inter prediction callers compute on the pictures of tests/ref_inter_cases.py, and of what
 ff_vvc_reconstruct computes on the pictures of tests/ref_recon_cases.py.
@@ -15,6 +15,8 @@ scratch, the intra weights and the patched .joint bytes; same rule.  Its digests
 MvField entries with the pad bytes zeroed.
 ref_recon.json holds per picture one digest of the inputs, one per plane after ff_vvc_reconstruct and one of the chroma scales the reference
 cached for the 64x64 units whose blocks the host routes to the TB passes; same rule.
+ref_picture.json holds per picture of tests/ref_picture_cases.py one digest of the inputs, one per plane after ff_vvc_reconstruct, one per plane
+after ff_vvc_lmcs_filter, tab_dmvr_mvf and the routed units' chroma scales, all from ref_decode_picture; same rule, layout-independent.
 Usage: python tools/gen_golden.py [--check | --replace]"""
 import hashlib
 import json
@@ -46,6 +48,11 @@ try:                  # ... or no RECON pictures yet (ref_recon.json is then lef
     import ref_recon_cases  # noqa: E402
 except ImportError:
     ref_recon_cases = None
+
+try:                  # ... or no whole-picture pin of prediction + reconstruction + inverse LMCS yet (ref_picture.json is then left alone)
+    import ref_picture_cases  # noqa: E402
+except ImportError:
+    ref_picture_cases = None
 
 try:                  # ... or no full-scale pictures yet (ref_extremes.json is then left alone)
     import extreme_cases  # noqa: E402
@@ -162,6 +169,16 @@ def generate_extremes(lib):
             "pictures": {name: extreme_cases.host_digests(lib, "ref", name) for name in extreme_cases.picture_names()}}
 
 
+def generate_picture(lib):
+    """The document of ref_picture.json: the reference's three calls per CTU over whole pictures (ref_decode_picture of
+    oracle/ref_shim_picture.c); nothing of the oracle's enters the file."""
+    return {"source": "reference picture chain (ff_vvc_predict_inter, ff_vvc_reconstruct with ff_vvc_predict_ciip, ff_vvc_lmcs_filter per CTU) through "
+                      "oracle/ref_shim_picture.c on tests/ref_picture_cases.py",
+            "format": "pictures[name][key] = sha256: inputs; the planes after reconstruction (r + component) and after inverse LMCS (p + component); "
+                      "dmvr = tab_dmvr_mvf, pad bytes zeroed; scale = (unit x, unit y, chroma scale) of the 64x64 units whose blocks go to the TB passes",
+            "pictures": {name: ref_picture_cases.reference_digests(lib, name) for name in ref_picture_cases.picture_names()}}
+
+
 def changed_digests(old, new):
     """Groups of `old` that `new` drops or records differently: [] when `new` only adds to `old`."""
     return [f"{slot}/{key}" for slot, grp in old.items() for key, rec in grp.items() if new.get(slot, {}).get(key) != rec]
@@ -180,8 +197,10 @@ def main():
     r_path = ref_recon_cases.GOLDEN_PATH if ref_recon_cases is not None else None
     extremes = dumps_passes(generate_extremes(lib)) if extreme_cases is not None else None
     x_path = extreme_cases.GOLDEN_PATH if extreme_cases is not None else None
+    whole = dumps_passes(generate_picture(lib)) if ref_picture_cases is not None else None
+    w_path = ref_picture_cases.GOLDEN_PATH if ref_picture_cases is not None else None
     if "--check" in sys.argv:
-        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon), (x_path, extremes)):
+        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon), (x_path, extremes), (w_path, whole)):
             if path is None:
                 continue
             if not os.path.exists(path):
@@ -199,6 +218,8 @@ def main():
             bad += changed_digests(ref_recon_cases.load_golden(), json.loads(recon)["pictures"])
         if x_path and os.path.exists(x_path):
             bad += changed_digests(extreme_cases.load_golden(), json.loads(extremes)["pictures"])
+        if w_path and os.path.exists(w_path):
+            bad += changed_digests(ref_picture_cases.load_golden(), json.loads(whole)["pictures"])
         if bad:
             sys.exit(f"{len(bad)} recorded groups would change or vanish (first: {bad[:4]}): nothing written; --replace if that is meant")
     with open(PATH, "w") as f:
@@ -220,6 +241,10 @@ def main():
         with open(x_path, "w") as f:
             f.write(extremes)
         print(f"wrote {x_path}: {len(json.loads(extremes)['pictures'])} pictures, {len(extremes)} bytes")
+    if w_path:
+        with open(w_path, "w") as f:
+            f.write(whole)
+        print(f"wrote {w_path}: {len(json.loads(whole)['pictures'])} pictures, {len(whole)} bytes")
 
 
 if __name__ == "__main__":
