@@ -210,6 +210,8 @@ BATCH_SIGNATURES = {
     # cu / tu records with their QP sidecars, the motion records and the four inter-unit lists in raster CTU order
     "rec_ctu_units":    ("i", "piiippi"),
     "rec_units":        ("i", "pp"),
+    # the transform-unit records the deblocking passes need (pcm bit, one chroma record per ISP unit, thin ISP partitions merged)
+    "rec_deblock_units": ("i", "pp"),
 }
 
 
@@ -998,6 +1000,11 @@ class RecUnitsResult(ctypes.Structure):
                 ("n_affine", ctypes.c_int32), ("n_gpm", ctypes.c_int32), ("n_ciip", ctypes.c_int32),
                 ("n_inter_jobs", ctypes.c_int32), ("n_affine_jobs", ctypes.c_int32), ("n_gpm_jobs", ctypes.c_int32), ("n_ciip_jobs", ctypes.c_int32),
                 ("ciip_scratch_len", ctypes.c_int32)]
+
+
+class RecDeblockTus(ctypes.Structure):
+    """Mirror of vvc355_rec_deblock_tus: the transform-unit records the deblocking passes need (HOST addresses)."""
+    _fields_ = [("tu", ctypes.c_uint64), ("tu_qp_c", ctypes.c_uint64), ("ctu_first_tu", ctypes.c_uint64), ("n_tu", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
 RECU_E_ARGS, RECU_E_MIXED, RECU_E_CIIP_SHAPE, RECU_E_MOTION, RECU_E_COUNT = range(-21, -26, -1)

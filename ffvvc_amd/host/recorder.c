@@ -25,7 +25,7 @@ enum { ST_IDLE, ST_BEGUN, ST_ENDED };
 enum { L_INTRA, L_INTER, L_TS, N_LISTS };
 enum { W_NO, W_YES, W_DEFERRED };
 enum { M_NONE, M_WALK, M_UNITS };                /* which of the two CTU entries the picture goes through */
-enum { U_CU, U_TU, U_MVF, U_INTER, U_AFFINE, U_GPM, U_CIIP, N_UNIT_LISTS };
+enum { U_CU, U_TU, U_MVF, U_INTER, U_AFFINE, U_GPM, U_CIIP, U_TUD, N_UNIT_LISTS };      /* U_TUD: the deblocking passes' transform-unit records */
 enum { N_KEYS = 2 * VVC355_INTER_TB_BINS };      /* the largest key space of the three lists */
 #define NO_SEQ 0xFFFFFFFFu
 
@@ -52,7 +52,7 @@ typedef struct rec_list {
     size_t pend_cap, out_cap, n, elem;
 } rec_list;
 static const size_t unit_elem[N_UNIT_LISTS] = { sizeof(vvc355_cu_rec), sizeof(vvc355_tu_rec), sizeof(vvc355_mvf_unit), sizeof(vvc355_inter_pu),
-                                                sizeof(vvc355_affine_cu), sizeof(vvc355_gpm_cu), sizeof(vvc355_ciip_cu) };
+                                                sizeof(vvc355_affine_cu), sizeof(vvc355_gpm_cu), sizeof(vvc355_ciip_cu), sizeof(vvc355_tu_rec) };
 
 struct vvc355_recorder {
     vvc355_rec_params p;
@@ -81,6 +81,9 @@ struct vvc355_recorder {
     int8_t *tu_qp, *tu_qp_out;    size_t tu_qp_cap, tu_qp_out_cap;      /* two bytes a record */
     int32_t *ctu_first[3];        size_t ctu_first_cap[3];              /* U_CU, U_TU, U_MVF */
     vvc355_rec_units_result units;
+    int8_t *tud_qp, *tud_qp_out;  size_t tud_qp_cap, tud_qp_out_cap;    /* U_TUD's sidecar and its ctu_first table */
+    int32_t *tud_first;           size_t tud_first_cap;
+    vvc355_rec_deblock_tus deblock;
 };
 
 static int grow_(void **p, size_t *cap, size_t n, size_t elem)
@@ -153,7 +156,7 @@ void vvc355_rec_destroy(vvc355_recorder *r)
     for (int l = 0; l < N_UNIT_LISTS; l++) {
         free(r->ul[l].pend); free(r->ul[l].out);
     }
-    free(r->cu_qp); free(r->cu_qp_out); free(r->tu_qp); free(r->tu_qp_out);
+    free(r->cu_qp); free(r->cu_qp_out); free(r->tu_qp); free(r->tu_qp_out); free(r->tud_qp); free(r->tud_qp_out); free(r->tud_first);
     for (int l = 0; l < 3; l++)
         free(r->ctu_first[l]);
     free(r);
@@ -514,6 +517,41 @@ static int record_unit(vvc355_recorder *r, int rs, int slice, const vvc355_rec_c
             q[0] = tree ? cu->qp[both ? 3 : 1] : 0, q[1] = tree ? cu->qp[both ? 3 : 2] : 0;
         }
     }
+    /* The deblocking passes' records (vvc355_rec_deblock_tus): one per call site of set_tb_pos (vvc_ctu.c:379-401), bit 4 (pcmf, :1246) where
+     * the unit is BDPCM-coded in that tree.  With ISP the chroma blocks belong to the last partition and cover the whole unit: ONE tree-1
+     * record over the coding unit.  ISP partitions 1 or 2 samples wide (high) share a 4-sample column (row) of the tables: one tree-0
+     * record per column (row), coded where any partition is. */
+    const int isp = cu->isp_type != 0 && cu->n_tus > 0;
+    const int thin_w = isp && cu->tus[0].w > 0 && cu->tus[0].w < 4, thin_h = isp && !thin_w && cu->tus[0].h > 0 && cu->tus[0].h < 4;
+    const int per = thin_w ? 4 / cu->tus[0].w : thin_h ? 4 / cu->tus[0].h : 1;
+    for (int tree = cu->tree_type == 2; tree < 1 + (chroma && cu->tree_type != 1); tree++) {
+        const uint8_t pcm = (uint8_t)((cu->bdpcm[tree ? 1 : 0] != 0) << 4);
+        const int step = tree ? 1 : per;
+        for (int i = (tree && isp) ? cu->n_tus - 1 : 0; i < cu->n_tus; i += step) {
+            const vvc355_rec_tu *tu = &cu->tus[i];
+            const int both = tu->joint_cbcr_residual_flag && tu->coded_flag[1] && tu->coded_flag[2];
+            vvc355_tu_rec *t = unit_push(r, U_TUD);
+            if (!t || GROW(r->tud_qp, r->tud_qp_cap, 2 * r->ul[U_TUD].n))
+                return VVC355_REC_E_NOMEM;
+            t->x0 = (int16_t)tu->x0, t->y0 = (int16_t)tu->y0, t->w = (uint8_t)tu->w, t->h = (uint8_t)tu->h;
+            if (tree) {
+                if (isp)
+                    t->x0 = (int16_t)cu->x0, t->y0 = (int16_t)cu->y0, t->w = (uint8_t)cu->w, t->h = (uint8_t)cu->h;
+                t->flags = (uint8_t)(0x80 | (tu->coded_flag[1] != 0) << 1 | (tu->coded_flag[2] != 0) << 2 | (tu->joint_cbcr_residual_flag != 0) << 3 | pcm);
+            } else {
+                int coded = 0;
+                for (int k = i; k < i + per && k < cu->n_tus; k++)
+                    coded |= cu->tus[k].coded_flag[0] != 0;
+                if (thin_w)
+                    t->w = 4;
+                if (thin_h)
+                    t->h = 4;
+                t->flags = (uint8_t)(coded | pcm);
+            }
+            int8_t *q = r->tud_qp + 2 * (r->ul[U_TUD].n - 1);
+            q[0] = tree ? cu->qp[both ? 3 : 1] : 0, q[1] = tree ? cu->qp[both ? 3 : 2] : 0;
+        }
+    }
     if (cu->tree_type == 2)
         return 0;
     if (!inter)                                       /* ff_vvc_set_intra_mvf: a zero MvField over the unit */
@@ -673,7 +711,7 @@ static int record_ctu(vvc355_recorder *r, int rs, int slice_flags, const vvc355_
     t->cmd_n = (uint32_t)r->n_pc - t->cmd_first, t->blk_n = (uint32_t)r->n_blk - t->blk_first;
     for (int l = 0; l < N_UNIT_LISTS; l++) {
         t->u_n[l] = (uint32_t)r->ul[l].n - t->u_first[l];
-        if (l <= U_MVF && t->u_n[l] > 65535)           /* what the device passes read of one CTU's range */
+        if ((l <= U_MVF || l == U_TUD) && t->u_n[l] > 65535)           /* what the device passes read of one CTU's range */
             return refuse(r, VVC355_RECU_E_COUNT);
     }
     return 0;
@@ -706,7 +744,8 @@ static int units_in_raster_order(vvc355_recorder *r)
         if (grow_((void **)&L->out, &L->out_cap, L->n + 1, L->elem) || (l <= U_MVF && GROW(r->ctu_first[l], r->ctu_first_cap[l], (size_t)n_ctu + 1)))
             return -1;
     }
-    if (GROW(r->cu_qp_out, r->cu_qp_out_cap, r->ul[U_CU].n + 1) || GROW(r->tu_qp_out, r->tu_qp_out_cap, 2 * r->ul[U_TU].n + 2))
+    if (GROW(r->cu_qp_out, r->cu_qp_out_cap, r->ul[U_CU].n + 1) || GROW(r->tu_qp_out, r->tu_qp_out_cap, 2 * r->ul[U_TU].n + 2) ||
+        GROW(r->tud_qp_out, r->tud_qp_out_cap, 2 * r->ul[U_TUD].n + 2) || GROW(r->tud_first, r->tud_first_cap, (size_t)n_ctu + 1))
         return -1;
     size_t at[N_UNIT_LISTS] = { 0 };
     for (int rs = 0; rs < n_ctu; rs++) {
@@ -715,6 +754,9 @@ static int units_in_raster_order(vvc355_recorder *r)
             memcpy(r->cu_qp_out + at[U_CU], r->cu_qp + t->u_first[U_CU], t->u_n[U_CU]);
         if (t->u_n[U_TU])
             memcpy(r->tu_qp_out + 2 * at[U_TU], r->tu_qp + 2 * (size_t)t->u_first[U_TU], 2 * (size_t)t->u_n[U_TU]);
+        if (t->u_n[U_TUD])
+            memcpy(r->tud_qp_out + 2 * at[U_TUD], r->tud_qp + 2 * (size_t)t->u_first[U_TUD], 2 * (size_t)t->u_n[U_TUD]);
+        r->tud_first[rs] = (int32_t)at[U_TUD];
         vvc355_mvf_unit *mv = (vvc355_mvf_unit *)r->ul[U_MVF].out + at[U_MVF];
         for (int l = 0; l < N_UNIT_LISTS; l++) {
             const rec_list *L = &r->ul[l];
@@ -731,6 +773,9 @@ static int units_in_raster_order(vvc355_recorder *r)
     }
     for (int l = 0; l <= U_MVF; l++)
         r->ctu_first[l][n_ctu] = (int32_t)at[l];
+    r->tud_first[n_ctu] = (int32_t)at[U_TUD];
+    r->deblock.tu = (const vvc355_tu_rec *)r->ul[U_TUD].out, r->deblock.tu_qp_c = r->tud_qp_out, r->deblock.ctu_first_tu = r->tud_first;
+    r->deblock.n_tu = (int32_t)at[U_TUD], r->deblock.pad_ = 0;
     vvc355_inter_pu *pu = (vvc355_inter_pu *)r->ul[U_INTER].out;
     for (size_t i = 0; i < at[U_INTER]; i++) {
         pu[i].first_job = (uint32_t)o->n_inter_jobs;
@@ -933,6 +978,20 @@ int vvc355_rec_units(const vvc355_recorder *r, vvc355_rec_units_result *out)
     if (r->mode == M_WALK)
         return VVC355_RECU_E_MIXED;
     *out = r->units;
+    return 0;
+}
+
+int vvc355_rec_deblock_units(const vvc355_recorder *r, vvc355_rec_deblock_tus *out)
+{
+    if (!r)
+        return VVC355_REC_E_ARGS;
+    if (!out)
+        return VVC355_RECU_E_ARGS;
+    if (r->state != ST_ENDED)
+        return VVC355_REC_E_STATE;
+    if (r->mode == M_WALK)
+        return VVC355_RECU_E_MIXED;
+    *out = r->deblock;
     return 0;
 }
 

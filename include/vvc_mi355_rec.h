@@ -17,7 +17,8 @@
  * list; every coded block of such a unit is KEEP, and their CTU counts as one that holds an intra unit) and records, from one
  * vvc355_rec_pu per coding unit, what the deblocking and motion side of a picture reads: the vvc355_cu_rec / vvc355_tu_rec lists with their
  * QP sidecars, the vvc355_mvf_unit list, and the vvc355_inter_pu / vvc355_affine_cu / vvc355_gpm_cu lists with their running job sums, all
- * grouped per CTU in raster order whatever the order of the calls (vvc355_rec_units after vvc355_rec_end_picture).
+ * grouped per CTU in raster order whatever the order of the calls (vvc355_rec_units after vvc355_rec_end_picture; the transform-unit
+ * records for the deblocking passes from vvc355_rec_deblock_units).
  * Of the statistics, keep counts a CIIP unit's blocks; walk_scaled and late_keep count what the neighbour rule above keeps, as before.
  *
  * Out of scope here: scaling lists, ACT; SAO / ALF / deblocking parameters stay with the caller.
@@ -181,7 +182,8 @@ typedef struct vvc355_rec_units_result {
     const vvc355_cu_rec *cu;               /* one per coding unit of the luma or single tree; flags = merge_subblock_flag | affine << 1 */
     const int8_t *cu_qp;                   /* paired by index: qp[0] */
     const vvc355_tu_rec *tu;               /* a tree-0 record per transform unit of a luma / single-tree unit, then (chroma formats) a tree-1
-                                            * record per transform unit of a chroma / single-tree unit, unit by unit */
+                                            * record per transform unit of a chroma / single-tree unit, unit by unit.  NOT what the deblocking
+                                            * passes need where a unit is BDPCM- or ISP-coded: vvc355_rec_deblock_units below */
     const int8_t *tu_qp_c;                 /* [n_tu][2]; read for tree-1 records: qp[1], qp[2], or qp[3] twice for a joint unit with both flags */
     const int32_t *ctu_first_cu, *ctu_first_tu;
     const vvc355_mvf_unit *mvf;            /* intra unit: PLAIN, zero body; PLAIN: one per sub-block; AFFINE (link = its affine_cu); GPM */
@@ -211,6 +213,24 @@ enum {
 int vvc355_rec_ctu_units(vvc355_recorder *rec, int rs, int slice_flags, int slice, const vvc355_rec_cu *cus, const vvc355_rec_pu *pus, int n_cus);
 /* After a vvc355_rec_end_picture that returned 0, for a picture recorded through vvc355_rec_ctu_units: fills *out; returns 0. */
 int vvc355_rec_units(const vvc355_recorder *rec, vvc355_rec_units_result *out);
+
+/* The transform-unit records for vvc355_tab_fill_pass, vvc355_deblock_bs_rec_pass and vvc355_deblock_qp_rec_pass, by the call sites of
+ * set_tb_pos / set_tb_tab / set_qp_c_tab (vvc_ctu.c:379-401, :1241-1250).  They differ from vvc355_rec_units_result.tu in three rules, each
+ * of which changes a boundary strength or a chroma QP (whole decoded pictures against the reference found them):
+ *   - bit 4 (pcm) is set where bdpcm[] of the tree's component is: two neighbouring BDPCM blocks get strength 0;
+ *   - an ISP unit has ONE tree-1 record, over the whole coding unit, with its last partition's flags and QPs (the chroma blocks belong to that
+ *     partition and cover the unit);
+ *   - ISP partitions 1 or 2 samples wide (high) share a 4-sample column (row) of the tables, and the passes skip rectangles that are no
+ *     multiples of 4: one tree-0 record per column (row), 4 wide (high), coded where any of its partitions is.
+ * Use them with vvc355_rec_units_result's cu, cu_qp and ctu_first_cu.  HOST pointers with the lifetime of vvc355_rec_result; 32 bytes. */
+typedef struct vvc355_rec_deblock_tus {
+    const vvc355_tu_rec *tu;
+    const int8_t *tu_qp_c;                 /* [n_tu][2], as vvc355_rec_units_result.tu_qp_c */
+    const int32_t *ctu_first_tu;           /* n_ctus + 1 entries */
+    int32_t  n_tu, pad_;
+} vvc355_rec_deblock_tus;
+/* Same conditions and refusals as vvc355_rec_units. */
+int vvc355_rec_deblock_units(const vvc355_recorder *rec, vvc355_rec_deblock_tus *out);
 
 #ifdef __cplusplus
 }

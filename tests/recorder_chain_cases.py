@@ -54,8 +54,10 @@ def ciip_inputs(pic, o_or_e, cmds):
 
 
 def content(pic, p):
-    """(dims, refs[list][ref][component], forward map) of a picture: ciip_frame_cases.pictures, seeded by the bit depth."""
-    return cf.pictures(np.random.default_rng([uc.SEED, pic.bd]), p, pic.bd)
+    """(dims, refs[list][ref][component], forward map) of a picture: ciip_frame_cases.pictures, seeded by the bit depth; a picture may carry
+    its own `content(p)` instead (the quiet pictures of ref_decoded_cases)."""
+    own = getattr(pic, "content", None)
+    return own(p) if own is not None else cf.pictures(np.random.default_rng([uc.SEED, pic.bd]), p, pic.bd)
 
 
 class GuardedPlane:

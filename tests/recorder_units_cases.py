@@ -233,6 +233,10 @@ def units_snapshot(lib, rec, n_ctus):
     s.inter, s.affine = rk._copy(u.inter, u.n_inter, INTER_PU), rk._copy(u.affine, u.n_affine, AFFINE_CU)
     s.gpm, s.ciip = rk._copy(u.gpm, u.n_gpm, GPM_CU), rk._copy(u.ciip, u.n_ciip, CIIP_CU)
     s.totals = {k: int(getattr(u, k)) for k in TOTALS}
+    d = abi.RecDeblockTus()
+    ret = lib.vvc355_rec_deblock_units(rec, ctypes.byref(d))
+    assert ret == 0, f"vvc355_rec_deblock_units: {ret}"
+    s.tud, s.tud_qp_c, s.first_tud = rk._copy(d.tu, d.n_tu, REC), rk._copy(d.tu_qp_c, 2 * d.n_tu, np.int8).reshape(-1, 2), rk._copy(d.ctu_first_tu, n_ctus + 1, np.int32)
     return s
 
 
@@ -401,11 +405,41 @@ def _qp8(v):
     return int(np.int8(v))
 
 
+def tu_records(pic, cu, tree):
+    """The DEBLOCKING transform-unit records (vvc355_rec_deblock_units) of one coding unit and tree, [(x0, y0, w, h, flags, (qp_cb, qp_cr))], by the call sites of set_tb_pos /
+    set_tb_tab (vvc_ctu.c:379-401, :1241-1250): one record per transform unit, bit 4 where the unit is BDPCM-coded in that tree (pcmf), but
+      * the chroma blocks of an ISP unit belong to its last partition and cover the WHOLE unit: one tree-1 record over the coding unit;
+      * ISP partitions 1 or 2 samples wide (high) share a 4-sample column (row) of the tables: one tree-0 record per column (row), coded
+        where any of its partitions is (every partition that carried a residual wrote the flag)."""
+    pcm = int(bool(cu["bdpcm"][1 if tree else 0])) << 4
+    if tree:
+        tus = cu["tus"][-1:] if cu["isp_type"] else cu["tus"]
+        out = []
+        for tu in tus:
+            both = tu["joint"] and tu["coded"][1] and tu["coded"][2]
+            rect = (cu["x0"], cu["y0"], cu["w"], cu["h"]) if cu["isp_type"] else (tu["x0"], tu["y0"], tu["w"], tu["h"])
+            out.append(rect + (0x80 | tu["coded"][1] << 1 | tu["coded"][2] << 2 | tu["joint"] << 3 | pcm,
+                               (_qp8(cu["qp"][3 if both else 1]), _qp8(cu["qp"][3 if both else 2]))))
+        return out
+    tus = cu["tus"]
+    if cu["isp_type"] and (tus[0]["w"] < 4 or tus[0]["h"] < 4):
+        ver = tus[0]["w"] < 4
+        per = 4 // (tus[0]["w"] if ver else tus[0]["h"])
+        out = []
+        for g in range(0, len(tus), per):
+            coded = int(any(tu["coded"][0] for tu in tus[g:g + per]))
+            rect = (tus[g]["x0"], tus[g]["y0"], 4, tus[g]["h"]) if ver else (tus[g]["x0"], tus[g]["y0"], tus[g]["w"], 4)
+            out.append(rect + (coded | pcm, (0, 0)))
+        return out
+    return [(tu["x0"], tu["y0"], tu["w"], tu["h"], tu["coded"][0] | pcm, (0, 0)) for tu in tus]
+
+
 def expect_units(pic, d):
     """The unit lists by the rules of INTEGRATION.md section 3, CTUs in raster order, decoding order inside a CTU: a namespace with the
     fields of units_snapshot()."""
     chroma = pic.idc != 0
-    cu_l, cu_qp, tu_l, tu_qp, mv_l, first = [], [], [], [], [], {k: [0] for k in ("cu", "tu", "mvf")}
+    cu_l, cu_qp, tu_l, tu_qp, mv_l, first = [], [], [], [], [], {k: [0] for k in ("cu", "tu", "mvf", "tud")}
+    tud_l, tud_qp = [], []
     inter, affine, gpm, ciip = [], [], [], []
     jobs = dict.fromkeys(TOTALS, 0)
     for rs, ctu in enumerate(pic.ctus):
@@ -422,6 +456,9 @@ def expect_units(pic, d):
                     flags = (0x80 | tu["coded"][1] << 1 | tu["coded"][2] << 2 | tu["joint"] << 3) if tree else tu["coded"][0]
                     tu_l.append((tu["x0"], tu["y0"], tu["w"], tu["h"], flags, 0))
                     tu_qp.append((_qp8(cu["qp"][3 if both else 1]), _qp8(cu["qp"][3 if both else 2])) if tree else (0, 0))
+                for (tx, ty, tw, th, flags, qp_c) in tu_records(pic, cu, tree):
+                    tud_l.append((tx, ty, tw, th, flags, 0))
+                    tud_qp.append(qp_c)
             if cu["tree_type"] == 2:
                 continue
             if pu is None:
@@ -449,11 +486,13 @@ def expect_units(pic, d):
                 mv_l.append(mu.gpm(x, y, w, h, pu["part"], parts[0], parts[1]))
                 gpm.append((x, y, w, h, pu["part"], sl, (0, 0), jobs["n_gpm_jobs"], pu["motion"].tobytes()))
                 jobs["n_gpm_jobs"] += tiles16(w) * tiles16(h) + (2 * tiles16(w >> pic.hs) * tiles16(h >> pic.vs) if chroma else 0)
-        first["cu"].append(len(cu_l)), first["tu"].append(len(tu_l)), first["mvf"].append(len(mv_l))
+        first["cu"].append(len(cu_l)), first["tu"].append(len(tu_l)), first["mvf"].append(len(mv_l)), first["tud"].append(len(tud_l))
     e = SimpleNamespace(totals=jobs)
     e.cu, e.tu = np.array(cu_l, REC) if cu_l else np.zeros(0, REC), np.array(tu_l, REC) if tu_l else np.zeros(0, REC)
     e.cu_qp, e.tu_qp_c = np.array(cu_qp, np.int8), np.array(tu_qp, np.int8).reshape(-1, 2)
     e.first_cu, e.first_tu, e.first_mvf = (np.array(first[k], np.int32) for k in ("cu", "tu", "mvf"))
+    e.tud, e.tud_qp_c = np.array(tud_l, REC) if tud_l else np.zeros(0, REC), np.array(tud_qp, np.int8).reshape(-1, 2)      # vvc355_rec_deblock_units
+    e.first_tud = np.array(first["tud"], np.int32)
     e.mvf = np.array(mv_l, UNIT) if mv_l else np.zeros(0, UNIT)
     e.inter = np.array(inter, INTER_PU) if inter else np.zeros(0, INTER_PU)
     e.affine = np.array(affine, AFFINE_CU) if affine else np.zeros(0, AFFINE_CU)
@@ -535,7 +574,7 @@ def unit_differences(pic, d, o):
         if got.dtype != want.dtype or got.shape != want.shape or got.tobytes() != want.tobytes():
             bad.append(name)
 
-    for k in ("first_cu", "first_tu", "first_mvf", "inter", "affine", "gpm", "ciip"):        # byte for byte
+    for k in ("first_cu", "first_tu", "first_mvf", "first_tud", "inter", "affine", "gpm", "ciip"):        # byte for byte
         cmp(k, getattr(u, k), getattr(e, k))
     if u.totals != e.totals:
         bad.append(f"totals {u.totals} against {e.totals}")
@@ -547,6 +586,9 @@ def unit_differences(pic, d, o):
         bad.append("cu records / cu_qp")
     if _per_ctu_sets(u.first_tu, u.tu, np.where(tree1, u.tu_qp_c, 0)) != _per_ctu_sets(e.first_tu, e.tu, e.tu_qp_c):
         bad.append("tu records / tu_qp_c")
+    tree1 = ((u.tud["flags"] & 0x80) != 0)[:, None]
+    if _per_ctu_sets(u.first_tud, u.tud, np.where(tree1, u.tud_qp_c, 0)) != _per_ctu_sets(e.first_tud, e.tud, e.tud_qp_c):
+        bad.append("deblocking tu records / their tu_qp_c")
     if _per_ctu_sets(u.first_mvf, u.mvf) != _per_ctu_sets(e.first_mvf, e.mvf):
         bad.append("mvf_unit records")
     # ... and through the tables they paint

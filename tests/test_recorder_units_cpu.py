@@ -33,7 +33,7 @@ from test_picture_cpu import _enum
 HEADER = os.path.join(ROOT, "include", "vvc_mi355_rec.h")
 SWEEP = 32
 MIRRORS = (("vvc355_rec_pu", abi.RecPu, 32), ("vvc355_rec_units_result", abi.RecUnitsResult, 144), ("vvc355_rec_cu", abi.RecCu, 56),
-           ("vvc355_rec_result", abi.RecResult, 416), ("vvc355_rec_params", abi.RecParams, 48))
+           ("vvc355_rec_result", abi.RecResult, 416), ("vvc355_rec_params", abi.RecParams, 48), ("vvc355_rec_deblock_tus", abi.RecDeblockTus, 32))
 CODES = ("ARGS", "MIXED", "CIIP_SHAPE", "MOTION", "COUNT")
 
 
@@ -245,6 +245,7 @@ def test_refusals_leave_the_recorder_usable(lib):
         res, ures = abi.RecResult(), abi.RecUnitsResult()
         assert lib.vvc355_rec_ctu_units(rec, 0, 0, 0, None, None, 0) == abi.REC_E_STATE          # no picture begun
         assert lib.vvc355_rec_units(rec, ctypes.byref(ures)) == abi.REC_E_STATE
+        assert lib.vvc355_rec_deblock_units(rec, ctypes.byref(abi.RecDeblockTus())) == abi.REC_E_STATE
         assert lib.vvc355_rec_ctu_units(None, 0, 0, 0, None, None, 0) == abi.REC_E_ARGS
         par = rk.params(pic)
 
@@ -312,6 +313,7 @@ def test_refusals_leave_the_recorder_usable(lib):
         assert rk.feed(lib, rec, plain_pic, q) == 0 and lib.vvc355_rec_end_picture(rec, ctypes.byref(res)) == 0
         assert lib.vvc355_rec_units(rec, ctypes.byref(ures)) == abi.RECU_E_MIXED
         assert lib.vvc355_rec_units(rec, None) == abi.RECU_E_ARGS
+        assert lib.vvc355_rec_deblock_units(rec, ctypes.byref(abi.RecDeblockTus())) == abi.RECU_E_MIXED and lib.vvc355_rec_deblock_units(rec, None) == abi.RECU_E_ARGS
         # more than 65535 records of a kind in one CTU: 65536 times the same 8x8 intra unit
         one = np.zeros(65536, rk.CU)
         one["w"], one["h"], one["pred_mode"] = 8, 8, 1

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Regenerate tests/golden/ref_slots.json, tests/golden/ref_passes.json, tests/golden/ref_inter.json, tests/golden/ref_recon.json,
-tests/golden/ref_picture.json and tests/golden/ref_extremes.json (the full-scale pictures of tests/extreme_cases.py, in the format of ref_passes.json / ref_inter.json): SHA-256
+tests/golden/ref_picture.json, tests/golden/ref_decoded.json and tests/golden/ref_extremes.json (the full-scale pictures of tests/extreme_cases.py, in the format of ref_passes.json / ref_inter.json): SHA-256
 digests of what the reference's own C path computes on the case lists of tests/ref_cases.py, of what its in-loop filter callers compute on
 the pictures of tests/ref_pass_cases.py, of what its inter prediction callers compute on the pictures of tests/ref_inter_cases.py, and of what
 ff_vvc_reconstruct computes on the pictures of tests/ref_recon_cases.py.
@@ -17,6 +17,9 @@ ref_recon.json holds per picture one digest of the inputs, one per plane after f
 cached for the 64x64 units whose blocks the host routes to the TB passes; same rule.
 ref_picture.json holds per picture of tests/ref_picture_cases.py one digest of the inputs, one per plane after ff_vvc_reconstruct, one per plane
 after ff_vvc_lmcs_filter, tab_dmvr_mvf and the routed units' chroma scales, all from ref_decode_picture; same rule, layout-independent.
+ref_decoded.json holds per picture of tests/ref_decoded_cases.py one digest of the inputs, tab_dmvr_mvf, the ten bS / filter-length tables and
+the QP tables the reference's deblocking read, and one per plane after the horizontal pass, SAO and ALF, from ref_decode_picture followed by
+ref_deblock_picture, ref_sao_picture and ref_alf_picture on its output; same rule.
 Usage: python tools/gen_golden.py [--check | --replace]"""
 import hashlib
 import json
@@ -58,6 +61,11 @@ try:                  # ... or no full-scale pictures yet (ref_extremes.json is 
     import extreme_cases  # noqa: E402
 except ImportError:
     extreme_cases = None
+
+try:                  # ... or no whole decoded pictures yet (ref_decoded.json is then left alone)
+    import ref_decoded_cases  # noqa: E402
+except ImportError:
+    ref_decoded_cases = None
 
 CONTEXT_SLOTS_AFTER = "ilfnst_transform"          # the context slots follow vvc_intra.c's static functions in the file
 
@@ -179,6 +187,17 @@ def generate_picture(lib):
             "pictures": {name: ref_picture_cases.reference_digests(lib, name) for name in ref_picture_cases.picture_names()}}
 
 
+def generate_decoded(lib, orc):
+    """The document of ref_decoded.json: the reference's picture chain followed by its three in-loop filter callers.  `orc` draws what the
+    description leaves to the reconstructed luma (the LADF bounds, from a plane ref_picture.json pins to the reference's); nothing the
+    oracle computed enters the file."""
+    return {"source": "reference picture chain (ref_decode_picture of oracle/ref_shim_picture.c) followed by ff_vvc_deblock_vertical / _horizontal, "
+                      "ff_vvc_sao_filter and ff_vvc_alf_filter (oracle/ref_shim_filter.c) on tests/ref_decoded_cases.py",
+            "format": "pictures[name][key] = sha256: inputs; dmvr = tab_dmvr_mvf, pad bytes zeroed; the ten bS / filter-length tables; the QP tables "
+                      "painted from the units; the planes after the horizontal pass, SAO and ALF (h, sao, alf + component)",
+            "pictures": {name: ref_decoded_cases.reference_digests(lib, orc, name) for name in ref_decoded_cases.picture_names()}}
+
+
 def changed_digests(old, new):
     """Groups of `old` that `new` drops or records differently: [] when `new` only adds to `old`."""
     return [f"{slot}/{key}" for slot, grp in old.items() for key, rec in grp.items() if new.get(slot, {}).get(key) != rec]
@@ -199,8 +218,10 @@ def main():
     x_path = extreme_cases.GOLDEN_PATH if extreme_cases is not None else None
     whole = dumps_passes(generate_picture(lib)) if ref_picture_cases is not None else None
     w_path = ref_picture_cases.GOLDEN_PATH if ref_picture_cases is not None else None
+    decoded = dumps_passes(generate_decoded(lib, ref_lib.load_oracle())) if ref_decoded_cases is not None else None
+    d_path = ref_decoded_cases.GOLDEN_PATH if ref_decoded_cases is not None else None
     if "--check" in sys.argv:
-        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon), (x_path, extremes), (w_path, whole)):
+        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon), (x_path, extremes), (w_path, whole), (d_path, decoded)):
             if path is None:
                 continue
             if not os.path.exists(path):
@@ -220,6 +241,8 @@ def main():
             bad += changed_digests(extreme_cases.load_golden(), json.loads(extremes)["pictures"])
         if w_path and os.path.exists(w_path):
             bad += changed_digests(ref_picture_cases.load_golden(), json.loads(whole)["pictures"])
+        if d_path and os.path.exists(d_path):
+            bad += changed_digests(ref_decoded_cases.load_golden(), json.loads(decoded)["pictures"])
         if bad:
             sys.exit(f"{len(bad)} recorded groups would change or vanish (first: {bad[:4]}): nothing written; --replace if that is meant")
     with open(PATH, "w") as f:
@@ -245,6 +268,10 @@ def main():
         with open(w_path, "w") as f:
             f.write(whole)
         print(f"wrote {w_path}: {len(json.loads(whole)['pictures'])} pictures, {len(whole)} bytes")
+    if d_path:
+        with open(d_path, "w") as f:
+            f.write(decoded)
+        print(f"wrote {d_path}: {len(json.loads(decoded)['pictures'])} pictures, {len(decoded)} bytes")
 
 
 if __name__ == "__main__":
