@@ -202,6 +202,15 @@ __device__ __forceinline__ StripRef pick3(int c, StripRef a, StripRef b, StripRe
 {
     return StripRef{ a.p + (c == 0 ? 0 : c == 1 ? (int)(b.p - a.p) : (int)(d.p - a.p)), c == 0 ? a.pitch : c == 1 ? b.pitch : d.pitch, c == 0 ? a.x0s : c == 1 ? b.x0s : d.x0s, false };
 }
+// the same for a wave that only ever sees one channel type (the RECON walk): ROLE 0 = luma, nothing to choose; ROLE 1 = Cb (c == 1) or Cr
+template <int ROLE, int BD> __device__ __forceinline__ GPix<BD> pick_role(int c, GPix<BD> a, GPix<BD> b, GPix<BD> d) { return GPix<BD>{ ROLE == 0 ? a.p : c == 1 ? b.p : d.p }; }
+template <int ROLE> __device__ __forceinline__ LPix pick_role(int c, LPix a, LPix b, LPix d) { return LPix{ a.p, ROLE == 0 ? a.base : c == 1 ? b.base : d.base }; }
+template <int ROLE> __device__ __forceinline__ StripRef pick_role(int c, StripRef a, StripRef b, StripRef d)
+{
+    if (ROLE == 0)
+        return StripRef{ a.p, a.pitch, a.x0s, false };
+    return StripRef{ b.p + (c == 1 ? 0 : (int)(d.p - b.p)), c == 1 ? b.pitch : d.pitch, c == 1 ? b.x0s : d.x0s, false };
+}
 
 // constant tables the predictors index per sample: straight from the device's constant arrays (batched kernels: many waves hide the
 // latency), or from a copy the RECON stage driver keeps in LDS (one wave walks a dependent chain there: every global round trip
@@ -1613,9 +1622,10 @@ __device__ __forceinline__ int recon_run(uint32_t line, int from)
     const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)line) >> from;
     return m == ~0u ? 32 : __builtin_ctz(~m);
 }
-// ff_vvc_get_top_available (vvc_intra.c:591-620), one wave (uniform arguments, uniform result)
+// ff_vvc_get_top_available (vvc_intra.c:591-620), one wave (uniform arguments, uniform result).  Inlined (both): a call takes the
+// CTU's context through the private segment.
 typedef uint32_t ReconMaps[2][2][32];
-__device__ int recon_top_available(const vvc355_recon_frame &f, const ReconCtx &cx, const ReconMaps &rmap, int cu_x0, int x, int y, int target, int c_idx)
+__device__ __forceinline__ int recon_top_available(const vvc355_recon_frame &f, const ReconCtx &cx, const ReconMaps &rmap, int cu_x0, int x, int y, int target, int c_idx)
 {
     const int hs = c_idx ? f.hs : 0, vs = c_idx ? f.vs : 0;
     const int end_of_ctb_x = ((cu_x0 >> f.ctb_log2) + 1) << f.ctb_log2;
@@ -1635,7 +1645,7 @@ __device__ int recon_top_available(const vvc355_recon_frame &f, const ReconCtx &
     return max(0, min(target, end - x));
 }
 // ff_vvc_get_left_available (vvc_intra.c:622-648), one wave
-__device__ int recon_left_available(const vvc355_recon_frame &f, const ReconCtx &cx, const ReconMaps &rmap, int cu_y0, int x, int y, int target, int c_idx)
+__device__ __forceinline__ int recon_left_available(const vvc355_recon_frame &f, const ReconCtx &cx, const ReconMaps &rmap, int cu_y0, int x, int y, int target, int c_idx)
 {
     const int hs = c_idx ? f.hs : 0, vs = c_idx ? f.vs : 0;
     const int x0b = x & ((1 << (f.ctb_log2 - hs)) - 1);
@@ -1903,7 +1913,9 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
         // lane 0 adds 1, the other lanes 0: lane 0's return value is the ticket
         const int t = __hip_atomic_fetch_add(&state[0], tid == 0 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         L.bc[0] = __builtin_amdgcn_readfirstlane(t);
-        recon_luma_done_set(L, 0);
+        // -1: nothing of this CTU's luma is there yet, not even the edges its first shift() follows — a chroma wave whose command 0
+        // reads luma (CCLM, a scaled RESID) waits for `luma_done >= 0` like for any later command
+        recon_luma_done_set(L, -1);
     }
     __syncthreads();
     const int ticket = __builtin_amdgcn_readfirstlane(L.bc[0]);
@@ -1968,12 +1980,12 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
     // (a register pipeline of per-command global loads makes every rotation wait for the load issued last).
     static_assert(CMD_DW == 10, "cmdbuf holds windows of 10-dword commands");
     const uint32_t n_cmd = ctu.n_cmd;
-    uint16_t (*arr)[kEdgeLen] = L.arr[role];
     const LTabs tabs{ &L.tabs };
-    VVC355_LDS uint32_t *cbuf = (VVC355_LDS uint32_t *)L.cmdbuf[role];
     // plan (the walk's loads): every lane then plans its own command — one of this wave's — and writes the plan over the command's slot
     // (recon_plan.hpp).  Which commands the wave takes is decided on the raw kinds, before that.
-    auto load_window = [&](uint32_t base, uint32_t *all_kinds, auto plan) -> unsigned long long {
+    // (r = the calling wave's role: a run-time value in the pre-pass, a constant in each copy of the walk)
+    auto load_window = [&](const int r, uint32_t base, uint32_t *all_kinds, auto plan) -> unsigned long long {
+        VVC355_LDS uint32_t *cbuf = (VVC355_LDS uint32_t *)L.cmdbuf[r];
         const uint32_t n_dw = min(64u, n_cmd - base) * CMD_DW;
         const uint32_t *g = (const uint32_t *)(cmds + base);
         uint32_t v[CMD_DW];
@@ -1986,7 +1998,7 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
         group_sync<64>();
         const uint32_t kinds = cbuf[tid * CMD_DW + 6];
         *all_kinds = kinds;
-        const unsigned long long m = __ballot(base + (uint32_t)tid < n_cmd && ((((kinds >> 16) & 0xff) > 0) == (role == 1)) && ((kinds >> 8) & 0xff) != VVC355_RECON_MARK);
+        const unsigned long long m = __ballot(base + (uint32_t)tid < n_cmd && ((((kinds >> 16) & 0xff) > 0) == (r == 1)) && ((kinds >> 8) & 0xff) != VVC355_RECON_MARK);
         if constexpr (decltype(plan)::value) {
             const bool mine = (m >> tid) & 1;
             ReconPlan P;
@@ -2022,12 +2034,13 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
     // took its ticket ahead of its neighbours — the usual case on a dependency chain — does this while it would be waiting anyway.
     {
         ReconMaps &rmap = L.rmap[role];
+        VVC355_LDS uint32_t *cbuf = (VVC355_LDS uint32_t *)L.cmdbuf[role];
         ((uint32_t *)rmap)[tid] = 0;
         ((uint32_t *)rmap)[tid + 64] = 0;
         uint32_t *cmd_dw = (uint32_t *)cmds;
         for (uint32_t base = 0; base < n_cmd; base += 64) {
             uint32_t kinds;
-            (void)load_window(base, &kinds, std::false_type{});
+            (void)load_window(role, base, &kinds, std::false_type{});
             const uint32_t kind_l = (kinds >> 8) & 0xff, type_l = ((kinds >> 16) & 0xff) > 0;
             const bool in_l = base + (uint32_t)tid < n_cmd;
             const bool mine = type_l == (uint32_t)role;
@@ -2082,254 +2095,272 @@ __device__ __forceinline__ bool recon_one_ctu(const vvc355_recon_frame &f, Recon
     // LUMA only (flag raised as soon as a neighbour's luma commands are done; a LIGHT neighbour's luma was final before the pass), the
     // chroma wave the whole neighbour.  From here to the join at the end the two waves run on their own: each waits, loads its own edges
     // and walks its commands; where the chroma wave reads luma (CCLM, the chroma residual scale) it synchronises on luma_done.
-    const unsigned long long t_wait = RPROF_NOW();
-    if (role == 0) { RTRACE(rs, 0, wall_clock64()); RTRACE(rs, 6, ctu.flags | ((unsigned long long)ctu.n_cmd << 8)); }
-    {
-        const int n_ctus = ncx * f.ctb_height;
-        const int dep[4] = { rx > 0 ? rs - 1 : -1, (rx > 0 && ry > 0) ? rs - ncx - 1 : -1, ry > 0 ? rs - ncx : -1, (ry > 0 && rx + 1 < ncx) ? rs - ncx + 1 : -1 };
+    // That stretch is compiled once per role (walk, below): the luma wave's copy has c_idx == 0 throughout, and none of what only chroma
+    // commands use — the Cb / Cr twin, CCLM, the joint and scaled residuals; the chroma wave's copy chooses between Cb and Cr only.  No
+    // workgroup barrier lies inside it.
+    auto walk = [&](auto role_c) __attribute__((always_inline)) {
+        constexpr int kRole = decltype(role_c)::value;          // everything below takes the role from here, not from the run-time `role`
+        uint16_t (*arr)[kEdgeLen] = L.arr[kRole];
+        VVC355_LDS uint32_t *cbuf = (VVC355_LDS uint32_t *)L.cmdbuf[kRole];
+        const unsigned long long t_wait = RPROF_NOW();
+        if (kRole == 0) { RTRACE(rs, 0, wall_clock64()); RTRACE(rs, 6, ctu.flags | ((unsigned long long)ctu.n_cmd << 8)); }
+        {
+            const int n_ctus = ncx * f.ctb_height;
+            const int dep[4] = { rx > 0 ? rs - 1 : -1, (rx > 0 && ry > 0) ? rs - ncx - 1 : -1, ry > 0 ? rs - ncx : -1, (ry > 0 && rx + 1 < ncx) ? rs - ncx + 1 : -1 };
 #pragma unroll
-        for (int d = 0; d < 4; d++) {
-            if (dep[d] < 0 || __builtin_amdgcn_readfirstlane(gld<uint32_t>(&ctus[dep[d]].n_cmd)) == 0)
-                continue;
-            if (role == 0 && (__builtin_amdgcn_readfirstlane(gld<uint32_t>(&ctus[dep[d]].flags)) & VVC355_RECON_CTU_LIGHT))
-                continue;
-            VVC355_GLOBAL int *flag = &state[kReconFlags + (role == 0 ? n_ctus : 0) + dep[d]];
-            while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0)
-                __builtin_amdgcn_s_sleep(4);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    RPROF_ADD(1 + 32 * role, t_wait);
-    RPROF_INC(0 + 32 * role);
-    RTRACE(rs, role ? 3 : 1, wall_clock64());
-    const unsigned long long t_load = RPROF_NOW();
-    if constexpr (TILE) {
-        // what the neighbours wrote: left apron and the rows above
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const int sh = c ? 1 : 0;
-            if ((c == 0) == (role == 0))
-                recon_edges_load<BD>(tiles + kTileOff[c], c ? kBodyChromaP : kBodyLumaP, tiles + kStripOff[c], c ? kStripChromaP : kStripLumaP, (const uint8_t *)f.plane[c], f.stride[c],
-                                     (rx * ctb) >> sh, (ry * ctb) >> sh, ctb >> sh, ch0 >> sh, f.width >> sh, f.height >> sh, tid);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        group_sync<64>();
-    } else {
-        pl0 = GPix<BD>{ (uint8_t *)f.plane[0] }; pl1 = GPix<BD>{ (uint8_t *)f.plane[1] }; pl2 = GPix<BD>{ (uint8_t *)f.plane[2] };
-        ps0 = f.stride[0] / (int)sizeof(px_t); ps1 = f.stride[1] / (int)sizeof(px_t);
-    }
-
-    RPROF_ADD(2 + 32 * role, t_load);
-    const unsigned long long t_loop = RPROF_NOW();
-#ifdef VVC355_RECON_PROF
-    const long long c_loop = clock64();
-#endif
-    // The first advance() loads window 0: the window load, with its planner, has one call site in the walk (the loop's head, which a
-    // twin's second step goes through as well).
-    uint32_t win = (uint32_t)0 - 64u, kinds_unused;
-    unsigned long long mask = 0;
-    auto advance = [&]() -> int {         // index of the wave's next command, -1 when its list is exhausted
-        while (!mask) {
-            if (win + 64 >= n_cmd)
-                return -1;
-            win += 64;
-            mask = load_window(win, &kinds_unused, std::true_type{});
-        }
-        const int bit = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        return (int)win + bit;
-    };
-    auto load_cmd = [&](int idx) -> uint32_t { return cbuf[(idx - (int)win) * CMD_DW + min(tid, CMD_DW - 1)]; };      // lane i holds dword i
-    int i0 = -1;
-    // luma_done = every luma command below this index is finished (the chroma wave waits on it before CCLM)
-    auto shift = [&]() {
-        i0 = advance();
-        if (role == 0)
-            recon_luma_done_set(L, i0 >= 0 ? i0 : (int)n_cmd);          // issued after the finished command's stores (LDS: in order; planes: after s_waitcnt vmcnt(0))
-    };
-    int4 pre[4] = {};                    // residuals fetched one command ahead (the first 1024 of the block)
-    int pre_k = -1;
-    int lmcs_xv = -1, lmcs_yv = -1, lmcs_scale = 0;      // lc->lmcs: the 64x64 unit whose chroma residual scale is known (reset per CTU, vvc_intra.c:509-510)
-    int n_shift = 1;                     // 2 after a Cb / Cr twin: its second command is done as well
-    for (;;) {
-        do shift(); while (--n_shift);
-        if (i0 < 0)
-            break;
-        n_shift = 1;
-        const uint32_t k = (uint32_t)i0;
-        const int i1 = mask ? (int)win + __builtin_ctzll(mask) : -1;        // the wave's next command, when this window holds it
-        const uint32_t d0 = load_cmd(i0), d1 = i1 >= 0 ? load_cmd(i1) : 0u;
-        uint32_t p[CMD_DW];                  // the command's plan (recon_plan.hpp)
-#pragma unroll
-        for (int i = 0; i < CMD_DW; i++) p[i] = (uint32_t)__builtin_amdgcn_readlane((int)d0, i);
-        const int kind = (int)((p[6] >> 8) & 0xff);
-        if (i1 >= 0) {
-            const uint32_t n6 = (uint32_t)__builtin_amdgcn_readlane((int)d1, 6);
-            // the wave's next command is a residual block: start its first loads now, so that they travel while this command
-            // (usually that block's prediction) runs — unless this command is about to use the registers they go to
-            if (((n6 >> 8) & 0xff) == VVC355_RECON_RESID && pre_k != i0) {
-                const uint64_t ptr = (uint32_t)__builtin_amdgcn_readlane((int)d1, 0) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)d1, 1) << 32);
-                const uint32_t wh = (uint32_t)__builtin_amdgcn_readlane((int)d1, 3);
-                const int nn = (int)(wh & 0xffff) * (int)(wh >> 16);
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (tid * 4 + 256 * u < nn)
-                        pre[u] = gld<int4>((const int *)ptr + tid * 4 + 256 * u);
-                pre_k = i1;
+            for (int d = 0; d < 4; d++) {
+                if (dep[d] < 0 || __builtin_amdgcn_readfirstlane(gld<uint32_t>(&ctus[dep[d]].n_cmd)) == 0)
+                    continue;
+                if (kRole == 0 && (__builtin_amdgcn_readfirstlane(gld<uint32_t>(&ctus[dep[d]].flags)) & VVC355_RECON_CTU_LIGHT))
+                    continue;
+                VVC355_GLOBAL int *flag = &state[kReconFlags + (kRole == 0 ? n_ctus : 0) + dep[d]];
+                while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0)
+                    __builtin_amdgcn_s_sleep(4);
             }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        const unsigned long long t_cmd = RPROF_NOW();
-        if (kind == VVC355_RECON_PRED) {
-            const IntraSetup su = recon_plan_setup(p);
-            const uint32_t fl = p[8] >> 16;
-            RPROF_ADD(6 + 32 * role, t_cmd);
-            if (TILE && (fl & kPlanTwin)) {
-                if constexpr (TILE) {
-                    // Cb and its twin Cr in one pass: lanes 0-31 Cb, lanes 32-63 Cr — same plan, each half on its own tile, strip, edge
-                    // arrays and scratch
-                    const int half = tid >> 5;
-                    const LPix plane2{ pl1.p, half ? pl2.base : pl1.base };
-                    StripRef sr2{ st1.p + (half ? (int)(st2.p - st1.p) : 0), st1.pitch, st1.x0s, (fl & kPlanStrip) != 0 };
-                    intra_pred_run<BD, 32>(su, plane2, ps1, L.arr[1 + half], L.scratch[1 + half], tid & 31, sr2, tabs);
-                    group_sync<64>();
-                    n_shift = 2;
-                }
-            } else {
-                const PX plane = pick3(su.c_idx, pl0, pl1, pl2);
-                StripRef sr = pick3(su.c_idx, st0, st1, st2);
-                sr.on = (fl & kPlanStrip) != 0;
-                intra_pred_run<BD, 64>(su, plane, su.c_idx ? ps1 : ps0, arr, L.scratch[role], tid, sr, tabs);
-                if (TILE) group_sync<64>(); else recon_sync_mem();
+        RPROF_ADD(1 + 32 * kRole, t_wait);
+        RPROF_INC(0 + 32 * kRole);
+        RTRACE(rs, kRole ? 3 : 1, wall_clock64());
+        const unsigned long long t_load = RPROF_NOW();
+        if constexpr (TILE) {
+            // what the neighbours wrote: left apron and the rows above
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const int sh = c ? 1 : 0;
+                if ((c == 0) == (kRole == 0))
+                    recon_edges_load<BD>(tiles + kTileOff[c], c ? kBodyChromaP : kBodyLumaP, tiles + kStripOff[c], c ? kStripChromaP : kStripLumaP, (const uint8_t *)f.plane[c], f.stride[c],
+                                         (rx * ctb) >> sh, (ry * ctb) >> sh, ctb >> sh, ch0 >> sh, f.width >> sh, f.height >> sh, tid);
             }
-        } else if (kind == VVC355_RECON_CCLM) {
-            // the coding unit's luma (every luma command before this one) must be reconstructed
-            while (recon_luma_done_get(L) < (int)k)
-                __builtin_amdgcn_s_sleep(1);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             group_sync<64>();
-            vvc355_cclm_job j = {};
-            j.x0 = (int16_t)(p[2] & 0xffff); j.y0 = (int16_t)(p[2] >> 16); j.width = (int16_t)(p[3] & 0xffff); j.height = (int16_t)(p[3] >> 16);
-            j.top_avail_c = (int16_t)(p[9] >> 16);
-            j.left_avail_c = (int16_t)(p[9] & 0xffff);
-            j.mode = (uint8_t)(p[6] & 0xff); j.hs = f.hs; j.vs = f.vs;
-            j.avail_l = (uint8_t)(p[7] & 0xff);
-            j.avail_t = (uint8_t)((p[7] >> 8) & 0xff);
-            j.collocated = f.collocated;
-            j.ctu_boundary = (uint8_t)((p[7] >> 16) & 0xff);
-            StripRef s0 = st0, s1 = st1, s2 = st2;
-            s0.on = s1.on = s2.on = TILE && j.ctu_boundary;
-            cclm_body<BD, 64>(j, pl0, ps0, pl1, pl2, ps1, ps1, L.prm[1], tid, s0, s1, s2);
-            if (TILE) group_sync<64>(); else recon_sync_mem();
-        } else if (kind == VVC355_RECON_CIIP) {
-            // inter.put_ciip (vvc_inter_template.c:60) of a combined inter / intra block (pred_regular_luma / _chroma, vvc_inter.c:570-575,
-            // :632-638): the intra prediction the previous command left in the picture, weighted against the inter prediction of the
-            // batched stage (resid: w x h pixels, packed rows); joint = ciip_derive_intra_weight (:530-548)
-            const int c_idx = (int)((p[4] >> 8) & 0xff), lw = (int)(p[4] & 0xff), w = 1 << lw, n = (int)p[5];
-            const int stride = c_idx ? ps1 : ps0, iw = (int)((p[4] >> 16) & 0xff);
-            const PX dst = pick3(c_idx, pl0, pl1, pl2).at((int)p[2]);
-            const uint8_t *inter = (const uint8_t *)(p[0] | ((uint64_t)p[1] << 32));
-            for (int i = tid; i < n; i += 64) {
-                const int o = (i >> lw) * stride + (i & (w - 1));
-                dst.st(o, (dst.ld(o) * iw + ld_px<BD>(inter, i) * (4 - iw) + 2) >> 2);
-            }
-            if (TILE) group_sync<64>(); else recon_sync_mem();
         } else {
-            // RESID: itx.add_residual / add_residual_joint (vvcdsp_template.c:32,48) of the block the transform stage left in resid
-            const int c_idx = (int)((p[4] >> 8) & 0xff), lw = (int)(p[4] & 0xff), w = 1 << lw, n = (int)p[5];
-            const int stride = c_idx ? ps1 : ps0, joint = (int)((p[4] >> 16) & 0xff);
-            const PX dst = pick3(c_idx, pl0, pl1, pl2).at((int)p[2]);
-            const int *res = (const int *)(p[0] | ((uint64_t)p[1] << 32));
-            const bool have = pre_k == (int)k;
-            const bool scaled = (p[4] >> 24) != 0;
-            const int xv = (int16_t)(p[7] & 0xffff), yv = (int16_t)(p[7] >> 16);       // the 64x64 unit of the coding unit
-            if (scaled && (lmcs_xv != xv || lmcs_yv != yv)) {
-                // lmcs_derive_chroma_scale (vvc_intra_template.c:390-429): average of the reconstructed luma left of and above the 64x64 unit of
-                // the coding unit.  Every luma command before this one must be done (the unit's neighbours may be this CTU's own blocks).
+            pl0 = GPix<BD>{ (uint8_t *)f.plane[0] }; pl1 = GPix<BD>{ (uint8_t *)f.plane[1] }; pl2 = GPix<BD>{ (uint8_t *)f.plane[2] };
+            ps0 = f.stride[0] / (int)sizeof(px_t); ps1 = f.stride[1] / (int)sizeof(px_t);
+        }
+
+        RPROF_ADD(2 + 32 * kRole, t_load);
+        const unsigned long long t_loop = RPROF_NOW();
+#ifdef VVC355_RECON_PROF
+        const long long c_loop = clock64();
+#endif
+        // The first advance() loads window 0: the window load, with its planner, has one call site in the walk (the loop's head, which a
+        // twin's second step goes through as well).
+        uint32_t win = (uint32_t)0 - 64u, kinds_unused;
+        unsigned long long mask = 0;
+        auto advance = [&]() -> int {         // index of the wave's next command, -1 when its list is exhausted
+            while (!mask) {
+                if (win + 64 >= n_cmd)
+                    return -1;
+                win += 64;
+                const unsigned long long t_win = RPROF_NOW();
+                mask = load_window(kRole, win, &kinds_unused, std::true_type{});
+                RPROF_ADD(8 + 32 * kRole, t_win);          // the window's round trip and its planner
+                RPROF_INC(16 + 32 * kRole);
+            }
+            const int bit = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            return (int)win + bit;
+        };
+        auto load_cmd = [&](int idx) -> uint32_t { return cbuf[(idx - (int)win) * CMD_DW + min(tid, CMD_DW - 1)]; };      // lane i holds dword i
+        int i0 = -1;
+        // luma_done = every luma command below this index is finished (the chroma wave waits on it before CCLM)
+        auto shift = [&]() {
+            i0 = advance();
+            if (kRole == 0)
+                recon_luma_done_set(L, i0 >= 0 ? i0 : (int)n_cmd);          // issued after the finished command's stores (LDS: in order; planes: after s_waitcnt vmcnt(0))
+        };
+        int4 pre[4] = {};                    // residuals fetched one command ahead (the first 1024 of the block)
+        int pre_k = -1;
+        int lmcs_xv = -1, lmcs_yv = -1, lmcs_scale = 0;      // lc->lmcs: the 64x64 unit whose chroma residual scale is known (reset per CTU, vvc_intra.c:509-510)
+        int n_shift = 1;                     // 2 after a Cb / Cr twin: its second command is done as well
+        for (;;) {
+            do shift(); while (--n_shift);
+            if (i0 < 0)
+                break;
+            n_shift = 1;
+            const uint32_t k = (uint32_t)i0;
+            const int i1 = mask ? (int)win + __builtin_ctzll(mask) : -1;        // the wave's next command, when this window holds it
+            const uint32_t d0 = load_cmd(i0), d1 = i1 >= 0 ? load_cmd(i1) : 0u;
+            uint32_t p[CMD_DW];                  // the command's plan (recon_plan.hpp)
+#pragma unroll
+            for (int i = 0; i < CMD_DW; i++) p[i] = (uint32_t)__builtin_amdgcn_readlane((int)d0, i);
+            const int kind = (int)((p[6] >> 8) & 0xff);
+            if (i1 >= 0) {
+                const uint32_t n6 = (uint32_t)__builtin_amdgcn_readlane((int)d1, 6);
+                // the wave's next command is a residual block: start its first loads now, so that they travel while this command
+                // (usually that block's prediction) runs — unless this command is about to use the registers they go to
+                if (((n6 >> 8) & 0xff) == VVC355_RECON_RESID && pre_k != i0) {
+                    const uint64_t ptr = (uint32_t)__builtin_amdgcn_readlane((int)d1, 0) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)d1, 1) << 32);
+                    const uint32_t wh = (uint32_t)__builtin_amdgcn_readlane((int)d1, 3);
+                    const int nn = (int)(wh & 0xffff) * (int)(wh >> 16);
+#pragma unroll
+                    for (int u = 0; u < 4; u++)
+                        if (tid * 4 + 256 * u < nn)
+                            pre[u] = gld<int4>((const int *)ptr + tid * 4 + 256 * u);
+                    pre_k = i1;
+                }
+            }
+            const unsigned long long t_cmd = RPROF_NOW();
+            if (kind == VVC355_RECON_PRED) {
+                IntraSetup su = recon_plan_setup(p);
+                if (kRole == 0)
+                    su.c_idx = 0;
+                const uint32_t fl = p[8] >> 16;
+                RPROF_ADD(6 + 32 * kRole, t_cmd);
+                if (kRole == 1 && TILE && (fl & kPlanTwin)) {
+                    if constexpr (TILE) {
+                        // Cb and its twin Cr in one pass: lanes 0-31 Cb, lanes 32-63 Cr — same plan, each half on its own tile, strip, edge
+                        // arrays and scratch
+                        const int half = tid >> 5;
+                        const LPix plane2{ pl1.p, half ? pl2.base : pl1.base };
+                        StripRef sr2{ st1.p + (half ? (int)(st2.p - st1.p) : 0), st1.pitch, st1.x0s, (fl & kPlanStrip) != 0 };
+                        intra_pred_run<BD, 32>(su, plane2, ps1, L.arr[1 + half], L.scratch[1 + half], tid & 31, sr2, tabs);
+                        group_sync<64>();
+                        n_shift = 2;
+                    }
+                } else {
+                    const PX plane = pick_role<kRole>(su.c_idx, pl0, pl1, pl2);
+                    StripRef sr = pick_role<kRole>(su.c_idx, st0, st1, st2);
+                    sr.on = (fl & kPlanStrip) != 0;
+                    intra_pred_run<BD, 64>(su, plane, kRole ? ps1 : ps0, arr, L.scratch[kRole], tid, sr, tabs);
+                    if (TILE) group_sync<64>(); else recon_sync_mem();
+                }
+            } else if (kRole == 1 && kind == VVC355_RECON_CCLM) {
+                // the coding unit's luma (every luma command before this one) must be reconstructed
                 while (recon_luma_done_get(L) < (int)k)
                     __builtin_amdgcn_s_sleep(1);
                 group_sync<64>();
-                const int size_y = min(ctb, 64);
-                lmcs_xv = xv; lmcs_yv = yv;
-                const bool avail_t = (p[8] >> 17) & 1, avail_l = (p[8] >> 16) & 1;
-                StripRef s0 = st0;
-                s0.on = TILE && (lmcs_yv & ctb_mask) == 0;
-                int v = 0;
-                if (tid < size_y) {
-                    if (avail_l)
-                        v += pl0.ld((lmcs_yv + min(tid, min(f.height - lmcs_yv, size_y) - 1)) * ps0 + lmcs_xv - 1);        // lmcs_sum_samples: the last sample stands in beyond the picture
-                    if (avail_t) {
-                        const int xx = lmcs_xv + min(tid, min(f.width - lmcs_xv, size_y) - 1);
-                        v += s0.on ? s0.at(xx, -1) : pl0.ld((lmcs_yv - 1) * ps0 + xx);
-                    }
-                }
-#pragma unroll
-                for (int sft = 32; sft; sft >>= 1)
-                    v += __shfl_xor(v, sft, 64);
-                const int cnt = (avail_l ? size_y : 0) + (avail_t ? size_y : 0);
-                const int avg = cnt ? (v + (cnt >> 1)) >> ilog2i(cnt) : 1 << (BD - 1);
-                lmcs_scale = lmcs_scale_of_avg((const vvc355_lmcs_model *)f.lmcs_model, avg, tid);
-            }
-            auto resid_of = [&](int r) {                        // the joint sign / shift (pred_residual_joint), then lmcs_scale_chroma
-                if (joint & 1)
-                    r = (r * ((joint & 2) ? -1 : 1)) >> ((joint >> 2) & 1);
-                if (scaled) {
-                    const int v = clip_intp2(r, BD);
-                    r = v > 0 ? (v * lmcs_scale + (1 << 10)) >> 11 : -((-v * lmcs_scale + (1 << 10)) >> 11);
-                }
-                return r;
-            };
-            auto add4 = [&](int i, const int4 r4) {             // w >= 4: four samples of one row per lane and step
-                const int r[4] = { r4.x, r4.y, r4.z, r4.w };
-                const int o = (i >> lw) * stride + (i & (w - 1));
-                int d[4];
-                dst.ld4(o, d);
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                    d[q] = clip_px<BD>(d[q] + resid_of(r[q]));
-                dst.st4(o, d[0], d[1], d[2], d[3]);
-            };
-            if (w < 4) {
-                // the 1- and 2-sample-wide transform blocks of a vertically split ISP coding unit (get_luma_predict_unit, vvc_intra.c:216-226:
-                // predicted 4 wide, residuals added per sub-partition): one sample per lane and step, any column parity
+                vvc355_cclm_job j = {};
+                j.x0 = (int16_t)(p[2] & 0xffff); j.y0 = (int16_t)(p[2] >> 16); j.width = (int16_t)(p[3] & 0xffff); j.height = (int16_t)(p[3] >> 16);
+                j.top_avail_c = (int16_t)(p[9] >> 16);
+                j.left_avail_c = (int16_t)(p[9] & 0xffff);
+                j.mode = (uint8_t)(p[6] & 0xff); j.hs = f.hs; j.vs = f.vs;
+                j.avail_l = (uint8_t)(p[7] & 0xff);
+                j.avail_t = (uint8_t)((p[7] >> 8) & 0xff);
+                j.collocated = f.collocated;
+                j.ctu_boundary = (uint8_t)((p[7] >> 16) & 0xff);
+                StripRef s0 = st0, s1 = st1, s2 = st2;
+                s0.on = s1.on = s2.on = TILE && j.ctu_boundary;
+                cclm_body<BD, 64>(j, pl0, ps0, pl1, pl2, ps1, ps1, L.prm[1], tid, s0, s1, s2);
+                if (TILE) group_sync<64>(); else recon_sync_mem();
+            } else if (kind == VVC355_RECON_CIIP) {
+                // inter.put_ciip (vvc_inter_template.c:60) of a combined inter / intra block (pred_regular_luma / _chroma, vvc_inter.c:570-575,
+                // :632-638): the intra prediction the previous command left in the picture, weighted against the inter prediction of the
+                // batched stage (resid: w x h pixels, packed rows); joint = ciip_derive_intra_weight (:530-548)
+                const int c_idx = (int)((p[4] >> 8) & 0xff), lw = (int)(p[4] & 0xff), w = 1 << lw, n = (int)p[5];
+                const int stride = kRole ? ps1 : ps0, iw = (int)((p[4] >> 16) & 0xff);
+                const PX dst = pick_role<kRole>(c_idx, pl0, pl1, pl2).at((int)p[2]);
+                const uint8_t *inter = (const uint8_t *)(p[0] | ((uint64_t)p[1] << 32));
                 for (int i = tid; i < n; i += 64) {
                     const int o = (i >> lw) * stride + (i & (w - 1));
-                    dst.st(o, clip_px<BD>(dst.ld(o) + resid_of(gld<int>(res + i))));
+                    dst.st(o, (dst.ld(o) * iw + ld_px<BD>(inter, i) * (4 - iw) + 2) >> 2);
                 }
+                if (TILE) group_sync<64>(); else recon_sync_mem();
             } else {
+                // RESID: itx.add_residual / add_residual_joint (vvcdsp_template.c:32,48) of the block the transform stage left in resid
+                // The joint sign / shift and the chroma residual scale belong to chroma blocks (vvc355_recon_cmd.joint): the luma wave adds plainly.
+                const int c_idx = (int)((p[4] >> 8) & 0xff), lw = (int)(p[4] & 0xff), w = 1 << lw, n = (int)p[5];
+                const int stride = kRole ? ps1 : ps0, joint = kRole ? (int)((p[4] >> 16) & 0xff) : 0;
+                const PX dst = pick_role<kRole>(c_idx, pl0, pl1, pl2).at((int)p[2]);
+                const int *res = (const int *)(p[0] | ((uint64_t)p[1] << 32));
+                const bool have = pre_k == (int)k;
+                const bool scaled = kRole == 1 && (p[4] >> 24) != 0;
+                const int xv = (int16_t)(p[7] & 0xffff), yv = (int16_t)(p[7] >> 16);       // the 64x64 unit of the coding unit
+                if (scaled && (lmcs_xv != xv || lmcs_yv != yv)) {
+                    // lmcs_derive_chroma_scale (vvc_intra_template.c:390-429): average of the reconstructed luma left of and above the 64x64 unit of
+                    // the coding unit.  Every luma command before this one must be done (the unit's neighbours may be this CTU's own blocks).
+                    while (recon_luma_done_get(L) < (int)k)
+                        __builtin_amdgcn_s_sleep(1);
+                    group_sync<64>();
+                    const int size_y = min(ctb, 64);
+                    lmcs_xv = xv; lmcs_yv = yv;
+                    const bool avail_t = (p[8] >> 17) & 1, avail_l = (p[8] >> 16) & 1;
+                    StripRef s0 = st0;
+                    s0.on = TILE && (lmcs_yv & ctb_mask) == 0;
+                    int v = 0;
+                    if (tid < size_y) {
+                        if (avail_l)
+                            v += pl0.ld((lmcs_yv + min(tid, min(f.height - lmcs_yv, size_y) - 1)) * ps0 + lmcs_xv - 1);        // lmcs_sum_samples: the last sample stands in beyond the picture
+                        if (avail_t) {
+                            const int xx = lmcs_xv + min(tid, min(f.width - lmcs_xv, size_y) - 1);
+                            v += s0.on ? s0.at(xx, -1) : pl0.ld((lmcs_yv - 1) * ps0 + xx);
+                        }
+                    }
 #pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int i = tid * 4 + 256 * u;
-                    if (i < n)
-                        add4(i, have ? pre[u] : gld<int4>(res + i));
+                    for (int sft = 32; sft; sft >>= 1)
+                        v += __shfl_xor(v, sft, 64);
+                    const int cnt = (avail_l ? size_y : 0) + (avail_t ? size_y : 0);
+                    const int avg = cnt ? (v + (cnt >> 1)) >> ilog2i(cnt) : 1 << (BD - 1);
+                    lmcs_scale = lmcs_scale_of_avg((const vvc355_lmcs_model *)f.lmcs_model, avg, tid);
                 }
-                for (int i = tid * 4 + 1024; i < n; i += 256)
-                    add4(i, gld<int4>(res + i));
+                auto resid_of = [&](int r) {                        // the joint sign / shift (pred_residual_joint), then lmcs_scale_chroma
+                    if (joint & 1)
+                        r = (r * ((joint & 2) ? -1 : 1)) >> ((joint >> 2) & 1);
+                    if (scaled) {
+                        const int v = clip_intp2(r, BD);
+                        r = v > 0 ? (v * lmcs_scale + (1 << 10)) >> 11 : -((-v * lmcs_scale + (1 << 10)) >> 11);
+                    }
+                    return r;
+                };
+                auto add4 = [&](int i, const int4 r4) {             // w >= 4: four samples of one row per lane and step
+                    const int r[4] = { r4.x, r4.y, r4.z, r4.w };
+                    const int o = (i >> lw) * stride + (i & (w - 1));
+                    int d[4];
+                    dst.ld4(o, d);
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+                        d[q] = clip_px<BD>(d[q] + resid_of(r[q]));
+                    dst.st4(o, d[0], d[1], d[2], d[3]);
+                };
+                if (w < 4) {
+                    // the 1- and 2-sample-wide transform blocks of a vertically split ISP coding unit (get_luma_predict_unit, vvc_intra.c:216-226:
+                    // predicted 4 wide, residuals added per sub-partition): one sample per lane and step, any column parity
+                    for (int i = tid; i < n; i += 64) {
+                        const int o = (i >> lw) * stride + (i & (w - 1));
+                        dst.st(o, clip_px<BD>(dst.ld(o) + resid_of(gld<int>(res + i))));
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        const int i = tid * 4 + 256 * u;
+                        if (i < n)
+                            add4(i, have ? pre[u] : gld<int4>(res + i));
+                    }
+                    for (int i = tid * 4 + 1024; i < n; i += 256)
+                        add4(i, gld<int4>(res + i));
+                }
+                if (TILE) group_sync<64>(); else recon_sync_mem();
             }
-            if (TILE) group_sync<64>(); else recon_sync_mem();
+            RPROF_ADD(9 + kind + 32 * kRole, t_cmd);
+            RPROF_INC(17 + kind + 32 * kRole);
         }
-        RPROF_ADD(9 + kind + 32 * role, t_cmd);
-        RPROF_INC(17 + kind + 32 * role);
-    }
-    RPROF_ADD(3 + 32 * role, t_loop);
+        RPROF_ADD(3 + 32 * kRole, t_loop);
 #ifdef VVC355_RECON_PROF
-    { unsigned long long *p_ = rprof_lds(); p_[7 + 32 * role] = p_[7 + 32 * role] + (unsigned long long)(clock64() - c_loop); }
+        { unsigned long long *p_ = rprof_lds(); p_[7 + 32 * kRole] = p_[7 + 32 * kRole] + (unsigned long long)(clock64() - c_loop); }
 #endif
-    if (role == 0) {
-        // the luma wave is through: what other CTUs read of this CTU's luma (its last kApr rows and columns) goes out now and the luma flag
-        // goes up, ahead of the chroma wave — LIGHT CTUs next to this one wait for nothing else
-        if constexpr (TILE) {
-            const int nk = cw0 >> 2, nr = ch0;
-            recon_tile_store<BD, 5>(tiles + kTileOff[0], kBodyLumaP, (uint8_t *)f.plane[0], f.stride[0], rx * ctb, ry * ctb, max(nr - kApr, 0), nr, 0, nk, tid);
-            recon_tile_store<BD, 0>(tiles + kTileOff[0], kBodyLumaP, (uint8_t *)f.plane[0], f.stride[0], rx * ctb, ry * ctb, 0, max(nr - kApr, 0), nk - 1, nk, tid);
+        if (kRole == 0) {
+            // the luma wave is through: what other CTUs read of this CTU's luma (its last kApr rows and columns) goes out now and the luma flag
+            // goes up, ahead of the chroma wave — LIGHT CTUs next to this one wait for nothing else
+            if constexpr (TILE) {
+                const int nk = cw0 >> 2, nr = ch0;
+                recon_tile_store<BD, 5>(tiles + kTileOff[0], kBodyLumaP, (uint8_t *)f.plane[0], f.stride[0], rx * ctb, ry * ctb, max(nr - kApr, 0), nr, 0, nk, tid);
+                recon_tile_store<BD, 0>(tiles + kTileOff[0], kBodyLumaP, (uint8_t *)f.plane[0], f.stride[0], rx * ctb, ry * ctb, 0, max(nr - kApr, 0), nk - 1, nk, tid);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(&state[kReconFlags + ncx * f.ctb_height + rs], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            RTRACE(rs, 2, wall_clock64());
+        } else {
+            RTRACE(rs, 4, wall_clock64());
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(&state[kReconFlags + ncx * f.ctb_height + rs], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        RTRACE(rs, 2, wall_clock64());
-    } else {
-        RTRACE(rs, 4, wall_clock64());
-    }
+    };
+    if (role == 0)
+        walk(std::integral_constant<int, 0>{});
+    else
+        walk(std::integral_constant<int, 1>{});
     const unsigned long long t_join = RPROF_NOW();
     __syncthreads();
     RPROF_ADD(4 + 32 * role, t_join);

@@ -1678,7 +1678,8 @@ typedef struct vvc355_recon_cmd {
     int16_t  cb_width, cb_height;
     int8_t   mode;             /* cu->intra_pred_mode_y / _c as parsed (before the wide-angle mapping); CCLM: 81, 82, 83 */
     uint8_t  kind, c_idx, ref_idx, is_mip, mip_mode, mip_transposed, isp_split, bdpcm_flag;
-    uint8_t  joint;            /* RESID: bit 0 = add_residual_joint, bit 1 = c_sign negative, bit 2 = shift;
+    uint8_t  joint;            /* RESID of a chroma block (c_idx 1, 2; a luma RESID is a plain add: the add ignores its joint byte):
+                                * bit 0 = add_residual_joint, bit 1 = c_sign negative, bit 2 = shift;
                                 * bit 3 = chroma residual scaling (itransform's chroma_scale, vvc_intra.c:449: chroma block of more than 4 samples in
                                 * a slice with sh_lmcs_used_flag and ph_chroma_residual_scale_flag): the residual — after the joint sign / shift,
                                 * vvc_intra.c:180-182 — goes through lmcs_scale_chroma (vvc_intra_template.c:431) with the scale of the 64x64
