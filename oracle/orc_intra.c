@@ -427,6 +427,11 @@ static int cclm_ds_luma(const orc_cclm_job *j, int wide, int cx, int cy)
 #undef L
 }
 
+/* Test instrumentation (tests/recon_extreme_cases.py): while a stats block is registered, every CCLM block adds what its derivation and
+ * its linear model reached; what the function writes does not change. */
+static _Thread_local orc_cclm_stats *cclm_stats;
+ORC_API void orc_cclm_debug_stats(orc_cclm_stats *s) { cclm_stats = s; }
+
 /* vvc_intra_template.c:352 (+ :29-277).  Returns nothing; writes the Cb and Cr predictions of the block. */
 ORC_API void orc_intra_cclm_pred_flat(int bd, const orc_cclm_job *j)
 {
@@ -547,10 +552,27 @@ ORC_API void orc_intra_cclm_pred_flat(int bd, const orc_cclm_job *j)
             b[i] = vmin[i + 1] - ((a[i] * vmin[0]) >> k[i]);
         }
     }
+    if (cclm_stats) {
+        cclm_stats->blocks++;
+        cclm_stats->diff0 += have && !a[0] && !k[0] && !a[1] && !k[1];
+        for (int c = 0; c < 2; c++) {
+            cclm_stats->a_pos15 += a[c] == 15;
+            cclm_stats->a_neg15 += a[c] == -15;
+            cclm_stats->k_is_1 += k[c] == 1;
+            if (a[c] > cclm_stats->a_max) cclm_stats->a_max = a[c];
+            if (a[c] < cclm_stats->a_min) cclm_stats->a_min = a[c];
+        }
+    }
     /* --- linear model on the down-sampled luma (:29); the reference keeps dsy in a pixel-typed array */
     for (int yy = 0; yy < h; yy++)
         for (int xx = 0; xx < w; xx++) {
             const int dsy = cclm_ds_luma(j, wide, xx, yy);
+            if (cclm_stats)
+                for (int c = 0; c < 2; c++) {
+                    const int v = ((dsy * a[c]) >> k[c]) + b[c];
+                    cclm_stats->below0 += v < 0;
+                    cclm_stats->above_max += v > (1 << bd) - 1;
+                }
             for (int c = 0; c < 2; c++)
                 orc_st(cpl[c], (ptrdiff_t)(y + yy) * cs[c] + x + xx, orc_clip_px(((dsy * a[c]) >> k[c]) + b[c], bd), wide);
         }

@@ -307,6 +307,11 @@ typedef struct orc_lmcs_scale_job {
     uint16_t pad_[6];
 } orc_lmcs_scale_job;
 void orc_intra_cclm_pred_flat(int bd, const orc_cclm_job *job);
+/* test instrumentation: CCLM blocks predicted while registered (NULL: none), blocks on the diff = 0 branch, components with a = +15 / -15
+ * (the largest magnitude the derivation gives) and with k = 1, the largest and smallest a, samples of ((dsy * a) >> k) + b below 0 and
+ * above the maximum before the clip */
+typedef struct orc_cclm_stats { int64_t blocks, diff0, a_pos15, a_neg15, k_is_1, a_max, a_min, below0, above_max; } orc_cclm_stats;
+void orc_cclm_debug_stats(orc_cclm_stats *s);
 int  orc_lmcs_chroma_scale_flat(int bd, const orc_lmcs_scale_job *job);
 void orc_lmcs_scale_chroma_flat(int bd, const orc_lmcs_scale_job *job, int *dst, const int *coeff, int width, int height);
 int  orc_intra_pred_angle(int mode);

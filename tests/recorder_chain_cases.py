@@ -79,6 +79,55 @@ class GuardedPlane:
         return got[a:b]
 
 
+def recorded_stages(k, dev, pic, d, o, cmds, d_arena, d_planes, strides, ticket):
+    """The frames of the three TB record passes, the scale pass and the RECON walk from a recorder's snapshot `o`, its arrays uploaded as they
+    are through the pcs.Keep `k`: (stages, scaled, the device scale table, the device command array, the device slice / column / row maps)."""
+    res, bd = o.res, pic.bd
+    d_slice, d_col, d_row = (k.up(a) for a in (pic.slice_idx, pic.col_bd, pic.row_bd))
+    d_model = k.up(np.frombuffer(bytes(pic.model), np.uint8))
+    d_levels = k.up(o.levels)
+    n_i, n_e, n_s = res.n_intra, res.n_inter, res.n_ts
+
+    def side(first, n):
+        return k.up(o.lv[first:first + n].view(np.uint8) if n else np.zeros(16, np.uint8)).ptr
+
+    scaled = bool(pic.chroma_scale_flag)
+    d_table = k.up(np.full(d.tpic.ux * d.tpic.uy, -1, np.int16))
+    st = {}
+    if n_i:
+        f = abi.IntraTbFrame()
+        f.tus, f.coeffs, f.n_tus = k.up(o.intra).ptr, d_arena.ptr, n_i
+        for c in range(6):
+            f.class_first[c] = res.class_first[c]
+        f.range, f.bd = pic.rbits, bd
+        f.lv, f.levels = side(0, n_i), d_levels.ptr
+        st["intra_tb"] = k.frame(f)
+    for name, ty, recs, n, first, first_lv in (("inter_tb", abi.InterTbFrame, o.inter, n_e, res.bin_first, n_i),
+                                               ("ts_tb", abi.TsTbFrame, o.ts, n_s, res.ts_first, n_i + n_e)):
+        if not n:
+            continue
+        f = ty()
+        f.tus, f.coeffs, f.n_tus = k.up(recs).ptr, d_arena.ptr, n
+        for c in range(3):
+            f.plane[c], f.stride[c] = d_planes[c].ptr, strides[c]
+        f.width, f.height, f.hs, f.vs, f.size_y, f.range, f.bd = pic.width, pic.height, pic.hs, pic.vs, pic.size_y, pic.rbits, bd
+        f.scale_table = d_table.ptr if scaled else 0
+        dst = f.bin_first if name == "inter_tb" else f.class_first
+        for ch in range(2):
+            for b in range(len(first[ch])):
+                dst[ch][b] = first[ch][b]
+        f.lv, f.levels = side(first_lv, n), d_levels.ptr
+        st[name] = k.frame(f)
+    if scaled:
+        st["lmcs_scale"] = k.frame(rc.scale_frame(pic, d_planes[0].ptr, strides[0], d_table.ptr, d_model.ptr, d_slice.ptr, d_col.ptr, d_row.ptr))
+    d_state = batch.DeviceBuffer(dev.vvc355_recon_state_bytes(pic.ncx * pic.ncy))
+    k.keep.append(d_state)
+    d_cmds = k.up(cmds)
+    st["recon"] = k.frame(rc.recon_frame(pic, None, [b.ptr for b in d_planes], strides, d_cmds.ptr, k.up(o.ctus).ptr, k.up(ticket).ptr,
+                                         d_state.ptr, d_slice.ptr, d_col.ptr, d_row.ptr, d_model.ptr if scaled else 0, n_work=res.n_work))
+    return st, scaled, d_table, d_cmds, (d_slice, d_col, d_row)
+
+
 class RecordedCiip:
     """One picture with CIIP units recorded and uploaded; the stages' frames are filled from the two results."""
 
@@ -103,48 +152,8 @@ class RecordedCiip:
         assert ticket is None or (pcs.order_check(dev, o.ctus, pic.ncx, pic.ncy, self.ticket) == 0 and
                                   rc.order_defect(o.ctus, pic.ncx, pic.ncy, self.ticket) is None), "not launched"
         strides = self.strides = [p.shape[1] * pic.isz for p in self.host_planes]
-        d_slice, d_col, d_row = (k.up(a) for a in (pic.slice_idx, pic.col_bd, pic.row_bd))
-        d_model = k.up(np.frombuffer(bytes(pic.model), np.uint8))
-        d_levels = k.up(o.levels)
-        n_i, n_e, n_s = res.n_intra, res.n_inter, res.n_ts
-
-        def side(first, n):
-            return k.up(o.lv[first:first + n].view(np.uint8) if n else np.zeros(16, np.uint8)).ptr
-
-        self.scaled = bool(pic.chroma_scale_flag)
-        self.d_table = k.up(np.full(d.tpic.ux * d.tpic.uy, -1, np.int16))
-        st = {}
-        if n_i:
-            f = abi.IntraTbFrame()
-            f.tus, f.coeffs, f.n_tus = k.up(o.intra).ptr, self.d_arena.ptr, n_i
-            for c in range(6):
-                f.class_first[c] = res.class_first[c]
-            f.range, f.bd = pic.rbits, bd
-            f.lv, f.levels = side(0, n_i), d_levels.ptr
-            st["intra_tb"] = k.frame(f)
-        for name, ty, recs, n, first, first_lv in (("inter_tb", abi.InterTbFrame, o.inter, n_e, res.bin_first, n_i),
-                                                   ("ts_tb", abi.TsTbFrame, o.ts, n_s, res.ts_first, n_i + n_e)):
-            if not n:
-                continue
-            f = ty()
-            f.tus, f.coeffs, f.n_tus = k.up(recs).ptr, self.d_arena.ptr, n
-            for c in range(3):
-                f.plane[c], f.stride[c] = self.d_planes[c].ptr, strides[c]
-            f.width, f.height, f.hs, f.vs, f.size_y, f.range, f.bd = pic.width, pic.height, pic.hs, pic.vs, pic.size_y, pic.rbits, bd
-            f.scale_table = self.d_table.ptr if self.scaled else 0
-            dst = f.bin_first if name == "inter_tb" else f.class_first
-            for ch in range(2):
-                for b in range(len(first[ch])):
-                    dst[ch][b] = first[ch][b]
-            f.lv, f.levels = side(first_lv, n), d_levels.ptr
-            st[name] = k.frame(f)
-        if self.scaled:
-            st["lmcs_scale"] = k.frame(rc.scale_frame(pic, self.d_planes[0].ptr, strides[0], self.d_table.ptr, d_model.ptr, d_slice.ptr, d_col.ptr, d_row.ptr))
-        d_state = batch.DeviceBuffer(dev.vvc355_recon_state_bytes(pic.ncx * pic.ncy))
-        k.keep.append(d_state)
-        d_cmds = k.up(cmds)
-        st["recon"] = k.frame(rc.recon_frame(pic, None, [b.ptr for b in self.d_planes], strides, d_cmds.ptr, k.up(o.ctus).ptr, k.up(self.ticket).ptr,
-                                             d_state.ptr, d_slice.ptr, d_col.ptr, d_row.ptr, d_model.ptr if self.scaled else 0, n_work=res.n_work))
+        st, self.scaled, self.d_table, d_cmds, (d_slice, d_col, d_row) = recorded_stages(k, dev, pic, d, o, cmds, self.d_arena, self.d_planes, strides,
+                                                                                        self.ticket)
         # the CIIP stage: the recorder's records, the SAME command array
         p = self.p = ciip_inputs(pic, o.u, cmds)
         self.dims, self.refs, self.lut = content(pic, p)

@@ -15,6 +15,8 @@ and tile maps, chroma), then orc_recon_frame_pass.  Those modules are imported, 
 tests/test_ref_recon_gpu.py and tools/gen_golden.py; tests/golden/ref_recon.json holds the digests.
 
 Every picture is deterministic, at most 264x136, and starts from bipred_cases.smooth_picture planes, which stand for the inter prediction.
+draw() has hooks for other content, levels, unit kinds, modes and LMCS models (tests/recon_extreme_cases.py draws its worst-case pictures
+through them); unset, as for every picture listed or swept here, they leave the draw as it was, random stream included.
 Domain (what the generator draws; the shim returns -1 outside what its objects can hold and the tests fail on that): no CIIP unit (the CIIP
 command stays pinned through put_ciip and ref_inter_cases I0-I4), no scaling lists, act_enabled_flag 0, intra units at most 64x64, no intra
 chroma block under 4 samples wide or under 16 samples (the standard has none; the reference's predictors write 4 columns there, past the
@@ -165,11 +167,35 @@ def _level_limit(pic, lw, lh, qp, dep, tsf):
     return ((1 << 31) - 1 - ((1 << shift) >> 1)) // (scale * 16)
 
 
-def _levels(rng, pic, w, h, qp, dep, tsf, bdpcm=0, vert=0, lfnst=False, dct2=(True, True)):
-    """(levels (h, w) int32, nzw, nzh) inside the domain."""
+def _hooked_levels(pic, drawn, w, h, lim, tsf, bdpcm, vert, lfnst, dct2):
+    """What a levels= hook returned, held to the domain _levels() draws in: nothing is clipped or repaired here, a hook that leaves it fails."""
+    c, nzw, nzh = drawn
+    c = np.ascontiguousarray(c, np.int32)
+    assert c.shape == (h, w) and c.any() and np.abs(c.astype(np.int64)).max() <= lim, "a levels= hook left the dequant limit"
+    if lfnst:
+        allowed = np.zeros((h, w), bool)
+        for (x, y) in DIAG4[:itc.lfnst_nz(w, h)]:
+            allowed[y, x] = True
+        assert not c[~allowed].any(), "LFNST levels outside the coded scan positions"
+    else:
+        mw, mh = (w, h) if tsf else (min(w, 32 if dct2[0] else 16), min(h, 32 if dct2[1] else 16))
+        assert 1 <= nzw <= mw and 1 <= nzh <= mh, "a level window beyond the zero-out"
+    assert not c[nzh:].any() and not c[:, nzw:].any(), "levels outside their window"
+    if bdpcm:
+        assert np.abs(np.cumsum(c.astype(np.int64), axis=0 if vert else 1)).max() <= min(lim, (1 << pic.rbits) - 1)
+    return c, int(nzw), int(nzh)
+
+
+def _levels(rng, pic, w, h, qp, dep, tsf, bdpcm=0, vert=0, lfnst=False, dct2=(True, True), cu=None, c_idx=0):
+    """(levels (h, w) int32, nzw, nzh) inside the domain.  A picture drawn with levels= asks its hook first (None: the draw below)."""
     lw, lh = w.bit_length() - 1, h.bit_length() - 1
     lim = _level_limit(pic, lw, lh, qp, dep, tsf)
     assert lim >= 1
+    hook = getattr(pic, "levels_hook", None)
+    if hook is not None:
+        drawn = hook(rng, pic, w, h, qp, dep, tsf, bdpcm=bdpcm, vert=vert, lfnst=lfnst, dct2=dct2, lim=lim, cu=cu, c_idx=c_idx)
+        if drawn is not None:
+            return _hooked_levels(pic, drawn, w, h, lim, tsf, bdpcm, vert, lfnst, dct2)
     if lfnst:
         c = np.zeros((h, w), np.int32)
         for (x, y) in DIAG4[:itc.lfnst_nz(w, h)]:
@@ -207,7 +233,7 @@ def _new_cu(x, y, w, h, pred_mode, tree=0):
 
 def _draw_qp(rng, pic):
     off = 6 * (pic.bd - 8)
-    hi = min(63 + off, MAX_TB_QP)
+    hi = min(63 + off, MAX_TB_QP, getattr(pic, "qp_max", MAX_TB_QP))
     lo = 0 if rng.random() < 0.15 else 12
     return [int(rng.integers(lo, hi + 1)) - off] + [int(rng.integers(lo, hi + 1)) for _ in range(3)]
 
@@ -231,9 +257,28 @@ def _chroma_tbs(rng, pic, cu, tu, x0, y0, w, h, ts_ok, sl):
         tsf = int(bool(tsf_tu))
         lf = bool(cu["apply_lfnst"][c]) and not tsf
         qp = tb_qp(pic, cu, tu, c, tsf)
-        lv, nzw, nzh = _levels(rng, pic, cw, ch, qp, sl[0], tsf, bd_c, cu["mode_c"] == 50, lf)
+        lv, nzw, nzh = _levels(rng, pic, cw, ch, qp, sl[0], tsf, bd_c, cu["mode_c"] == 50, lf, cu=cu, c_idx=c)
         out.append(_tb(c, x0, y0, cw, ch, 1, tsf, lv, nzw, nzh))
     return out
+
+
+def _hooked_modes(pic, cu, forced, ctb):
+    """What a modes= hook asks of an intra unit whose tools are drawn: prediction modes only, where the drawn tools leave them free."""
+    for k, v in (forced or {}).items():
+        if k == "mode_y":
+            assert cu["tree_type"] != 2 and not cu["mip_flag"] and not cu["bdpcm"][0] and 0 <= v <= 66 and (v != 0 or not cu["ref_idx"])
+        elif k == "mode_c":
+            assert pic.idc and cu["tree_type"] != 1 and not cu["bdpcm"][1] and (0 <= v <= 66 or 81 <= v <= 83)
+            cu["mip_chroma_direct"] = 0
+        elif k == "ref_idx":
+            assert 0 <= v <= 2 and (v == 0 or (cu["tree_type"] != 2 and not cu["isp_type"] and not cu["mip_flag"] and not cu["bdpcm"][0] and
+                                               forced.get("mode_y", cu["mode_y"]) != 0 and (cu["y0"] & (ctb - 1))))
+        elif k == "mip_mode":
+            size_id = 0 if (cu["w"] == 4 and cu["h"] == 4) else 1 if (cu["w"] == 4 or cu["h"] == 4 or (cu["w"] == 8 and cu["h"] == 8)) else 2
+            assert cu["mip_flag"] and 0 <= v < (16, 8, 6)[size_id]
+        else:
+            assert k == "mip_transposed" and cu["mip_flag"] and v in (0, 1), k
+        cu[k] = int(v)
 
 
 def _intra_cu(rng, pic, x, y, w, h, tree, sl):
@@ -288,6 +333,8 @@ def _intra_cu(rng, pic, x, y, w, h, tree, sl):
             cu["mode_c"], cu["mip_chroma_direct"] = int(rng.choice([18, 50])), 0
         if tree == 2 and not cu["bdpcm"][1] and cw >= 4 and ch >= 4 and rng.random() < t["lfnst"]:
             cu["lfnst_idx"], cu["apply_lfnst"][1], cu["apply_lfnst"][2] = int(rng.integers(1, 3)), 1, 1
+    if getattr(pic, "modes_hook", None) is not None:
+        _hooked_modes(pic, cu, pic.modes_hook(pic, cu), ctb)
     for i, (px_, py, pw, ph) in enumerate(parts):
         tu = dict(x0=px_, y0=py, w=pw, h=ph, coded=[0, 0, 0], joint=0, tbs=[])
         if tree != 2:
@@ -297,7 +344,7 @@ def _intra_cu(rng, pic, x, y, w, h, tree, sl):
                 tsf = int(bool(ts_y))
                 qp = tb_qp(pic, cu, tu, 0, tsf)
                 lv, nzw, nzh = _levels(rng, pic, pw, ph, qp, sl[0], tsf, cu["bdpcm"][0], cu["mode_y"] == 50, bool(cu["apply_lfnst"][0]) and not tsf,
-                                       tr_kinds(pic, cu, 0, pw, ph))
+                                       tr_kinds(pic, cu, 0, pw, ph), cu=cu)
                 tu["tbs"].append(_tb(0, px_, py, pw, ph, 1, tsf, lv, nzw, nzh))
             else:
                 tu["tbs"].append(_tb(0, px_, py, pw, ph, 0))
@@ -308,12 +355,13 @@ def _intra_cu(rng, pic, x, y, w, h, tree, sl):
     return cu
 
 
-def _inter_cu(rng, pic, x, y, w, h, sl):
-    """An inter coding unit: uncoded, or transform units per 64x64 tile, or the two transform units of SBT with one of them coded."""
+def _inter_cu(rng, pic, x, y, w, h, sl, coded=None):
+    """An inter coding unit: uncoded (drawn, or coded=False), or transform units per 64x64 tile, or the two transform units of SBT with one
+    of them coded."""
     t = pic.tools
     cu = _new_cu(x, y, w, h, 0)
     cu["qp"] = _draw_qp(rng, pic)
-    if rng.random() >= t["cu_coded"]:
+    if (rng.random() >= t["cu_coded"]) if coded is None else not coded:
         cu["coded_flag"] = 0
         return cu
     tiles = [(x + dx, y + dy, min(w, 64), min(h, 64)) for dy in range(0, h, 64) for dx in range(0, w, 64)]
@@ -340,7 +388,7 @@ def _inter_cu(rng, pic, x, y, w, h, sl):
         if has:
             tsf = int(bool(ts_cu))
             qp = tb_qp(pic, cu, tu, 0, tsf)
-            lv, nzw, nzh = _levels(rng, pic, pw, ph, qp, sl[0], tsf, dct2=tr_kinds(pic, cu, 0, pw, ph))
+            lv, nzw, nzh = _levels(rng, pic, pw, ph, qp, sl[0], tsf, dct2=tr_kinds(pic, cu, 0, pw, ph), cu=cu)
             tu["tbs"].append(_tb(0, px_, py, pw, ph, 1, tsf, lv, nzw, nzh))
         else:
             tu["tbs"].append(_tb(0, px_, py, pw, ph, 0))
@@ -354,8 +402,17 @@ def _inter_cu(rng, pic, x, y, w, h, sl):
 
 
 def draw(name, seed, bd, idc, ctb_log2, size, intra=1.0, slices=((0, 0),), lmcs=False, tiles=False, wpp=0, collocated=0, rbits=15, dual=False,
-         big_inter=False, inter_ctu=0.0, min_cu=8, mts=True, explicit_mts=False, min_qp_prime_ts=0, joint_sign=0, tools=None, angular=0):
-    """The unit-level description of one picture."""
+         big_inter=False, inter_ctu=0.0, min_cu=8, mts=True, explicit_mts=False, min_qp_prime_ts=0, joint_sign=0, tools=None, angular=0,
+         content=None, levels=None, units=None, modes=None, model=None, qp_max=MAX_TB_QP, partition=None):
+    """The unit-level description of one picture.  The hooks default to what is drawn here (every listed and swept picture: none set):
+      content(rng, pic, dims) -> the three starting planes, dims = [(h, w)] * 3 (4:0:0: two unused planes of half size);
+      levels(rng, pic, w, h, qp, dep, ts, bdpcm=, vert=, lfnst=, dct2=, lim=, cu=, c_idx=) -> (levels, nzw, nzh) of one coded block, or None
+          for the draw of _levels(); dct2 is tr_kinds()'s pair, lim the dequant limit of the block; the result is held to the domain;
+      units(pic, rs, x, y, w, h) -> "intra" / "inter" / "skip" (an inter unit without residual) for one leaf of the partition, or None;
+      modes(pic, cu) -> {mode_y, mode_c, ref_idx, mip_mode, mip_transposed} to force on an intra unit whose tools are drawn, or None;
+      partition(pic, rs) -> the leaves [(x, y, w, h)] of a single-tree CTU in coding order (power-of-two sides, tiling the CTU's part of the
+          picture), or None for the drawn partition;
+      model(bd) -> the LMCS model of a picture with lmcs=True; qp_max: the largest QP _draw_qp draws."""
     rng = np.random.default_rng(seed)
     W, H = size
     hs, vs = FMT[idc]
@@ -365,7 +422,8 @@ def draw(name, seed, bd, idc, ctb_log2, size, intra=1.0, slices=((0, 0),), lmcs=
     pic = SimpleNamespace(name=name, bd=bd, idc=idc, hs=hs, vs=vs, ctb_log2=ctb_log2, width=W, height=H, ncx=ncx, ncy=ncy, rbits=rbits, wpp=wpp,
                           collocated=collocated, mts_enabled=int(mts), explicit_mts_intra=int(mts and explicit_mts), explicit_mts_inter=int(mts and explicit_mts),
                           min_qp_prime_ts=min_qp_prime_ts, joint_sign=joint_sign, chroma_scale_flag=int(lmcs and idc != 0), slices=[tuple(s) for s in slices],
-                          tools=dict(DEFAULT_TOOLS, **(tools or {})), size_y=min(ctb, 64), isz=1 if bd == 8 else 2, angular=angular)
+                          tools=dict(DEFAULT_TOOLS, **(tools or {})), size_y=min(ctb, 64), isz=1 if bd == 8 else 2, angular=angular,
+                          levels_hook=levels, modes_hook=modes, qp_max=qp_max)
     n_sl = len(pic.slices)
     cuts = sorted(rng.choice(np.arange(1, n_ctb), size=n_sl - 1, replace=False).tolist()) if n_sl > 1 else []
     pic.slice_idx = np.searchsorted(cuts, np.arange(n_ctb), side="right").astype(np.int16)
@@ -375,23 +433,36 @@ def draw(name, seed, bd, idc, ctb_log2, size, intra=1.0, slices=((0, 0),), lmcs=
         pic.row_bd = np.array([0 if y < cy else cy for y in range(ncy)] + [ncy], np.int16)
     else:
         pic.col_bd, pic.row_bd = np.array([0] * ncx + [ncx], np.int16), np.array([0] * ncy + [ncy], np.int16)
-    pic.model = recon_cases.ReconWork.lmcs_model(rng, bd) if lmcs else abi.LmcsModel()
+    pic.model = (model(bd) if model is not None else recon_cases.ReconWork.lmcs_model(rng, bd)) if lmcs else abi.LmcsModel()
     dims = [(H, W)] + [((H >> vs, W >> hs) if idc else (H >> 1, W >> 1))] * 2
-    if lmcs:
+    if content is not None:
+        pic.planes = [np.ascontiguousarray(p, px(bd)) for p in content(rng, pic, dims)]
+        assert [p.shape for p in pic.planes] == dims and all(int(p.max()) < (1 << bd) for p in pic.planes)
+    elif lmcs:
         # an own DC level per 32x32 unit under the smooth content: neighbouring 64x64 units then fall into different bins of the model
         luma = bc.smooth_picture(rng, H, W, bd).astype(np.int64) // 4 + np.kron(rng.integers(0, 3 << (bd - 2), size=((H + 31) // 32, (W + 31) // 32)),
                                                                                  np.ones((32, 32), np.int64))[:H, :W]
         planes = [np.clip(luma, 0, (1 << bd) - 1).astype(px(bd))]
     else:
         planes = [bc.smooth_picture(rng, H, W, bd)]
-    pic.planes = planes + [bc.smooth_picture(rng, dh, dw, bd) for (dh, dw) in dims[1:]]
+    if content is None:
+        pic.planes = planes + [bc.smooth_picture(rng, dh, dw, bd) for (dh, dw) in dims[1:]]
     pic.ctus = []
     whole_inter = rng.random(n_ctb) < inter_ctu
     for rs in range(n_ctb):
         rx, ry = rs % ncx, rs // ncx
         sl = pic.slices[int(pic.slice_idx[rs])]
         leaves, cus = [], []
-        _split(rng, rx * ctb, ry * ctb, ctb, ctb, W, H, min_cu, leaves, big_inter)
+        directed = partition(pic, rs) if partition is not None and not dual else None
+        if directed is None:
+            _split(rng, rx * ctb, ry * ctb, ctb, ctb, W, H, min_cu, leaves, big_inter)
+        else:
+            leaves = [tuple(v) for v in directed]
+            cover = np.zeros((min(ctb, H - ry * ctb), min(ctb, W - rx * ctb)), np.int32)
+            for (x, y, w, h) in leaves:
+                assert w & (w - 1) == 0 and h & (h - 1) == 0 and min(w, h) >= 4 and x % min(w, 8) == 0 and y % min(h, 8) == 0
+                cover[y - ry * ctb:y - ry * ctb + h, x - rx * ctb:x - rx * ctb + w] += 1
+            assert (cover == 1).all() and sum(w * h for (_x, _y, w, h) in leaves) == cover.size, "a directed partition does not tile its CTU"
         if dual:
             for (x, y, w, h) in leaves:
                 cus.append(_intra_cu(rng, pic, x, y, w, h, 1, sl))
@@ -405,8 +476,14 @@ def draw(name, seed, bd, idc, ctb_log2, size, intra=1.0, slices=((0, 0),), lmcs=
                 # there); units too small for that are inter units here, down to 4x4, which the standard does not have but the reference's
                 # and the record passes' residual paths do: their 2x2 chroma blocks are the ones chroma residual scaling leaves alone
                 small_c = idc != 0 and ((w >> hs) < 4 or (w >> hs) * (h >> vs) < 16)
-                is_intra = not whole_inter[rs] and not small_c and w <= 64 and h <= 64 and rng.random() < intra
-                cus.append(_intra_cu(rng, pic, x, y, w, h, 0, sl) if is_intra else _inter_cu(rng, pic, x, y, w, h, sl))
+                forced = units(pic, rs, x, y, w, h) if units is not None else None
+                if forced is None:
+                    is_intra = not whole_inter[rs] and not small_c and w <= 64 and h <= 64 and rng.random() < intra
+                else:
+                    is_intra = forced == "intra"
+                    assert forced in ("intra", "inter", "skip") and not (is_intra and (small_c or w > 64 or h > 64)), forced
+                cus.append(_intra_cu(rng, pic, x, y, w, h, 0, sl) if is_intra else
+                           _inter_cu(rng, pic, x, y, w, h, sl, coded=False if forced == "skip" else None))
         pic.ctus.append(cus)
     return pic
 

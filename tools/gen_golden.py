@@ -17,6 +17,7 @@ ref_recon.json holds per picture one digest of the inputs, one per plane after f
 cached for the 64x64 units whose blocks the host routes to the TB passes; same rule.
 ref_picture.json holds per picture of tests/ref_picture_cases.py one digest of the inputs, one per plane after ff_vvc_reconstruct, one per plane
 after ff_vvc_lmcs_filter, tab_dmvr_mvf and the routed units' chroma scales, all from ref_decode_picture; same rule, layout-independent.
+ref_recon_extremes.json holds the same record as ref_recon.json per directed worst-case picture of tests/recon_extreme_cases.py; same rule.
 ref_decoded.json holds per picture of tests/ref_decoded_cases.py one digest of the inputs, tab_dmvr_mvf, the ten bS / filter-length tables and
 the QP tables the reference's deblocking read, and one per plane after the horizontal pass, SAO and ALF, from ref_decode_picture followed by
 ref_deblock_picture, ref_sao_picture and ref_alf_picture on its output; same rule.
@@ -66,6 +67,11 @@ try:                  # ... or no whole decoded pictures yet (ref_decoded.json i
     import ref_decoded_cases  # noqa: E402
 except ImportError:
     ref_decoded_cases = None
+
+try:                  # ... or no worst-case RECON pictures yet (ref_recon_extremes.json is then left alone)
+    import recon_extreme_cases  # noqa: E402
+except ImportError:
+    recon_extreme_cases = None
 
 CONTEXT_SLOTS_AFTER = "ilfnst_transform"          # the context slots follow vvc_intra.c's static functions in the file
 
@@ -167,6 +173,15 @@ def generate_recon(lib):
             "pictures": {name: ref_recon_cases.reference_digests(lib, name) for name in ref_recon_cases.picture_names()}}
 
 
+def generate_recon_extremes(lib):
+    """The document of ref_recon_extremes.json: the reference's RECON walk over the directed worst-case pictures; nothing of the oracle's
+    enters the file."""
+    return {"source": "reference RECON stage (ff_vvc_reconstruct per CTU) through oracle/ref_shim_intra.c on tests/recon_extreme_cases.py",
+            "format": "pictures[name][key] = sha256: inputs; the planes after reconstruction (p + component); scale = (unit x, unit y, chroma scale) of "
+                      "the 64x64 units whose blocks go to the TB passes, as the reference cached them",
+            "pictures": {name: recon_extreme_cases.reference_digests(lib, name) for name in recon_extreme_cases.picture_names()}}
+
+
 def generate_extremes(lib):
     """The document of ref_extremes.json: the reference's whole-picture runs on the full-scale pictures of tests/extreme_cases.py; nothing of
     the oracle's enters the file."""
@@ -220,8 +235,11 @@ def main():
     w_path = ref_picture_cases.GOLDEN_PATH if ref_picture_cases is not None else None
     decoded = dumps_passes(generate_decoded(lib, ref_lib.load_oracle())) if ref_decoded_cases is not None else None
     d_path = ref_decoded_cases.GOLDEN_PATH if ref_decoded_cases is not None else None
+    rx = dumps_passes(generate_recon_extremes(lib)) if recon_extreme_cases is not None else None
+    rx_path = recon_extreme_cases.GOLDEN_PATH if recon_extreme_cases is not None else None
     if "--check" in sys.argv:
-        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon), (x_path, extremes), (w_path, whole), (d_path, decoded)):
+        for path, want in ((PATH, text), (p_path, passes), (i_path, inter), (r_path, recon), (x_path, extremes), (w_path, whole), (d_path, decoded),
+                           (rx_path, rx)):
             if path is None:
                 continue
             if not os.path.exists(path):
@@ -243,6 +261,8 @@ def main():
             bad += changed_digests(ref_picture_cases.load_golden(), json.loads(whole)["pictures"])
         if d_path and os.path.exists(d_path):
             bad += changed_digests(ref_decoded_cases.load_golden(), json.loads(decoded)["pictures"])
+        if rx_path and os.path.exists(rx_path):
+            bad += changed_digests(recon_extreme_cases.load_golden(), json.loads(rx)["pictures"])
         if bad:
             sys.exit(f"{len(bad)} recorded groups would change or vanish (first: {bad[:4]}): nothing written; --replace if that is meant")
     with open(PATH, "w") as f:
@@ -272,6 +292,11 @@ def main():
         with open(d_path, "w") as f:
             f.write(decoded)
         print(f"wrote {d_path}: {len(json.loads(decoded)['pictures'])} pictures, {len(decoded)} bytes")
+
+    if rx_path:
+        with open(rx_path, "w") as f:
+            f.write(rx)
+        print(f"wrote {rx_path}: {len(json.loads(rx)['pictures'])} pictures, {len(rx)} bytes")
 
 
 if __name__ == "__main__":
